@@ -6,14 +6,19 @@ frame encoder (BASELINE.json configs[1]) over B*T = 256 synthetic u8 224x224 fra
 fp32 accumulate; inputs are resident in HBM before the timed region.  Frames shard across ranks with no
 data-path collective (weak scaling: 256 frames per rank per step).
 
-    python bench.py [--gpus N --steps K --warmup W] [--model ViT-L/14 --frames 256 --dtype bf16]
+    python bench.py [--gpus N --steps K --warmup W] [--model ViT-L/14 --frames 256 --dtype bf16] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  ``--dump-outputs
+DIR`` then writes the embeddings of the last timed step to DIR/embeddings.npy (float32; ranks > 0 of an N-rank run write
+embeddings_rank<r>.npy); inputs and weights are seeded, so two builds can be compared output for output.  ``--full`` adds every
+other measurement below (f16 beside bf16, student and TFAM legs, rooflines, clock probe, CPU baseline and oracle parity).
 
 ``--gpus N`` with no WORLD_SIZE in the environment starts the N ranks itself: the parent process (which never touches a
 GPU) spawns N children of this script with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set, relays
 rank 0's JSON line and exits non-zero if any rank fails.  Under ``python -m torch.distributed.run`` (WORLD_SIZE set) it is one
 of the ranks.  One rank per GPU, RCCL backend.
 
-Prints ONE JSON line on rank 0.  `roofline` is the MFMA roofline of the dominant kernel family (the
+Prints ONE JSON line on rank 0.  With ``--full``, `roofline` is the MFMA roofline of the dominant kernel family (the
 vmc_linear GEMMs): algorithmic FLOPs of every GEMM launch of K instrumented steps divided by the HIP-event
 duration of exactly those launches.  `cpu_baseline` times the CPU oracle (oracle/vit.py, fp32 PyTorch) on a
 bounded sample of the same workload on this host's cores.
@@ -52,6 +57,40 @@ def _time_cuda(fn, iters, warmup=3):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / iters
+
+
+def host_threads() -> int:
+    # one GPU comes with a 16-core share of the host; more threads than that only oversubscribe
+    return min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+
+
+def vit_state_dict_threaded(name: str, seed: int) -> dict:
+    """synth.vit_state_dict with its synth.normal calls spread over host threads: the same tensors (each is a pure function of
+    seed, stream name and index), ~300 M ViT-L/14 values in seconds instead of half a minute of one core (numpy releases the GIL
+    in the element-wise passes)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from vimo_clip_amd import synth
+    normal = synth.normal
+    with ThreadPoolExecutor(host_threads()) as ex:
+        synth.normal = lambda *a, **kw: ex.submit(normal, *a, **kw)
+        try:
+            futures = synth.vit_state_dict(name, seed)
+        finally:
+            synth.normal = normal
+        return {k: f.result() for k, f in futures.items()}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, out: torch.Tensor, rank: int, world: int) -> None:
+    """The [frames, E] fp32 embeddings of one step as DIR/embeddings.npy; above 64 MB every k-th frame (fixed rows)."""
+    import numpy as np
+    stride = -(-out.numel() * 4 // DUMP_MAX_BYTES)
+    a = out[::stride].float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "embeddings.npy" if world == 1 else f"embeddings_rank{rank}.npy"), a)
 
 
 def spawn_ranks(n: int, argv) -> int:
@@ -510,9 +549,12 @@ def main():
     ap.add_argument("--model", default="ViT-L/14")
     ap.add_argument("--frames", type=int, default=256, help="frames per rank per step (B*T)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's embeddings to DIR/embeddings.npy")
+    ap.add_argument("--full", action="store_true", help="every measurement beside the headline (f16, student / TFAM legs, "
+                                                        "rooflines, clock probe, CPU baseline, oracle parity)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and oracle parity")
     ap.add_argument("--cpu-frames", type=int, default=8)
-    ap.add_argument("--no-extras", action="store_true", help="skip the TFAM measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the f16, student and TFAM measurements")
     ap.add_argument("--no-fuse-add-ln", action="store_true", help="A/B: residual add in the GEMM epilogue + plain LayerNorm")
     ap.add_argument("--selftest-spawn", action="store_true", help="CPU/gloo rehearsal of the --gpus N spawn path (tests)")
     ap.add_argument("--only", default="", choices=["", "tfam"], help="builder shortcut: run one secondary leg alone and print it")
@@ -552,7 +594,7 @@ def main():
         print(json.dumps(tfam_extras(dev, rank, world, cdt)), flush=True)
         return
     model = VisionTransformer.from_name(args.model, compute_dtype=cdt).to(dev).eval()
-    sd = synth.vit_state_dict(args.model, seed=2)
+    sd = vit_state_dict_threaded(args.model, seed=2)
     model.load_state_dict(sd, strict=True)
     model.frame_chunk = args.chunk or args.frames
     if args.no_fuse_add_ln:
@@ -585,6 +627,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
 
     total_frames = args.frames * args.steps * world
     fps = total_frames / elapsed
@@ -617,7 +661,7 @@ def main():
     # The parity claim "within 1e-3 fp16" of BASELINE.json's north_star belongs to the f16 compute type; the headline
     # runs in bf16 as configs[1] names it.  The same workload in f16, a few steps, beside it (one GPU only).
     y16_sample = None
-    if world == 1 and args.dtype == "bf16" and not args.no_extras:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.no_extras:
         try:
             m16 = VisionTransformer.from_name(args.model, compute_dtype=torch.float16).to(dev).eval()
             m16.load_state_dict(sd, strict=True)
@@ -630,10 +674,10 @@ def main():
         except Exception as e:      # noqa: BLE001
             result["f16_same_workload"] = {"error": f"{type(e).__name__}: {e}"}
 
-    y_sample = out[:8].float().cpu()       # the timed dtype's embeddings of the first frames (parity block below)
+    y_sample = out[:8].float().cpu() if args.full else None     # the timed dtype's embeddings of the first frames (parity block below)
     # secondary measurements never take the headline down with them: a failure is reported inside the JSON line, and every
     # leg with collectives agrees on its set-up across ranks before it enters them (all_ranks_ok)
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         def guarded(leg):
             if world > 1:
                 return leg()                        # a rank that dies takes the job down (the parent reports it); no silent hang
@@ -649,7 +693,7 @@ def main():
             except Exception as e:      # noqa: BLE001
                 result["tfam_forward"] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             # ---- roofline of the GEMM family: instrument every vmc_linear launch with HIP events --------
             events = []
@@ -746,8 +790,7 @@ def main():
         try:
             if not args.no_cpu_baseline and world == 1:     # reported at N = 1 only
                 from oracle import vit as ovit
-                # the GPU box gives one GPU a 16-core CPU share; more threads than that only oversubscribes
-                ncpu = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+                ncpu = host_threads()
                 torch.set_num_threads(ncpu)
                 nf = args.cpu_frames
                 pix = ovit.normalize_u8(frames[:nf].cpu())
@@ -780,6 +823,7 @@ def main():
                         result["cpu_baseline"]["tfam_forward"] = {"error": f"{type(e).__name__}: {e}"}
         except Exception as e:      # noqa: BLE001
             result["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
+    if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()

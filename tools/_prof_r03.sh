@@ -3,8 +3,8 @@ set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03f
 mkdir -p $O
-timeout -k 10 600 python3 bench.py > $O/bench_line.json 2> $O/bench.err
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/ks.log 2>&1
+timeout -k 10 600 python3 bench.py --full > $O/bench_line.json 2> $O/bench.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/ks.log 2>&1
 find $O/ks -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/bench_kernel_stats.csv
 rm -rf $O/ks
 for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
@@ -13,7 +13,7 @@ for c in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_VALU_MFMA_BUSY_CYC
 done
 python3 tools/pmc_summary.py gemm8p_kernel $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_TCC_HIT_sum $O/pmc_SQ_VALU_MFMA_BUSY_CYCLES > $O/gemm8_pmc.txt
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_TCC_HIT_sum $O/pmc_SQ_VALU_MFMA_BUSY_CYCLES
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/es -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/es.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/es -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras > $O/es.log 2>&1
 find $O/es -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $O/encoder_step_kernel_stats.csv
 rm -rf $O/es
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tf -- python3 tools/tfam_chain_run.py 8 100 > $O/tf.log 2>&1
