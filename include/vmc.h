@@ -258,10 +258,13 @@ int vmc_attention_vit_fwd(const void* qkv, void* out, float* lse, int F, int N, 
  *   out 16-bit [F, D].  Same kernel, one 16-row query tile per (frame, head) instead of ceil(N/16). */
 int vmc_attention_vit_cls_fwd(const void* q_cls, const void* kv, void* out, int F, int N, int H, int dtype16, void* stream);
 
-/* K4/K11/K12 generic masked attention (fp32 math), any head_dim <= 128 with head_dim % 8 == 0.
+/* K4/K11/K12 generic masked attention, any head_dim <= 128 with head_dim % 8 == 0.
  * Replaces F.multi_head_attention_forward's core (q*dh^-1/2, key_padding_mask -> -inf, softmax, @V)
  * for the TFAM self/cross attention (TFAM/models/AMO_CLIP.py:39-45) and serves as the backward's
  * forward-recompute reference.
+ *   head_dim 64 / 96: MFMA kernels with NO length limit (Tk <= 64: one wave per (b, h); longer: tiled kernels
+ *   streaming 64-key tiles with an online softmax); other head dims: fp32 scalar kernels, Tq, Tk <= 2048
+ *   (VMC_E_SHAPE beyond).  The tiled kernels also need out 8-byte aligned; otherwise the scalar kernel runs.
  *   q  16-bit, element (b, t, h, d) at q[(b*Tq + t)*ldq + h*dh + d];  k, v likewise with Tk, ldk, ldv
  *   key_mask u8 [B, Tk], 1 = attend, 0 = padding (the reference's mask_rgb/mask_flow), may be NULL
  *   out 16-bit [(b*Tq+t)*ldo + h*dh + d];  lse f32 [B,H,Tq] optional.
@@ -274,7 +277,10 @@ int vmc_attention_fwd(const void* q, const void* k, const void* v, const uint8_t
                       float* lse, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo,
                       float dropout_p, uint64_t dropout_seed, int dtype16, void* stream);
 /* Backward of the above (autograd of the MHA core, train.py:104 / TFAM/train_and_eval.py:82): dq, dk, dv
- * 16-bit with their own row strides, fully overwritten.  workspace >= vmc_attention_bwd_workspace_bytes. */
+ * 16-bit with their own row strides, fully overwritten.  workspace >= vmc_attention_bwd_workspace_bytes.
+ *   head_dim 64 / 96 with lddq, lddk, lddv, ldo % 4 == 0: MFMA, no length limit (Q, K, V, dO of a head in LDS when they fit
+ *   in 160 KB; longer: tiled two-pass kernels, no atomics, deterministic; these also need dq, dk, dv 8-byte and out 16-byte
+ *   aligned); otherwise fp32 scalar kernels, Tq, Tk <= 2048. */
 size_t vmc_attention_bwd_workspace_bytes(int B, int H, int Tq);
 int vmc_attention_bwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, const void* out,
                       const void* dout, const float* lse, void* dq, void* dk, void* dv,

@@ -1,7 +1,12 @@
 // Attention kernels (gfx950).
 //   vmc_attention_vit_fwd : CLIP ViT self-attention, head_dim 64, no mask — MFMA, whole K/V head in LDS.
-//   vmc_attention_fwd/bwd : generic masked attention in fp32 (TFAM self/cross attention; also the
-//                           training backward of the ViT blocks).
+//   vmc_attention_fwd/bwd : generic masked attention (TFAM self/cross attention; also the training backward of the ViT
+//                           blocks).  Dispatch, head_dim 64 / 96:
+//                             forward  Tk <= 64                       attn_small_kernel (one wave per (b, h))
+//                                      Tk > 64                        attention_long.hip (tiled, any length)
+//                             backward Q, K, V, dO of a head in LDS   attn_bwd_mfma_kernel
+//                                      longer                         attention_long.hip (tiled, any length)
+//                           other head dims (<= 128, % 8): the scalar fp32 kernels below, Tq, Tk <= 2048.
 #include "common.h"
 
 // ==================================================================================================
@@ -897,10 +902,21 @@ static int launch_bwd_mfma(const void* q, const void* k, const void* v, const ui
 
 static int check_generic(int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo) {
   if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return VMC_E_ARG;
-  if (dh <= 0 || dh > ATT_MAX_DH || (dh % 8) || Tk > ATT_MAX_TK || Tq > ATT_MAX_TK) return VMC_E_SHAPE;
+  if (dh <= 0 || dh > ATT_MAX_DH || (dh % 8)) return VMC_E_SHAPE;
   if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8)) return VMC_E_ALIGN;
   return 0;
 }
+// the scalar kernels keep a score row in LDS: ATT_MAX_TK floats
+static int check_scalar_len(int Tq, int Tk) { return (Tk > ATT_MAX_TK || Tq > ATT_MAX_TK) ? VMC_E_SHAPE : 0; }
+
+// Tiled kernels of attention_long.hip.  Beyond check_generic they store 16-bit results as 8-byte words (output bases 8-byte
+// aligned, output strides % 4) and the backward reads O as 16-byte words; a caller that does not give that alignment keeps
+// the scalar kernels.
+int attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out, float* lse, int B, int H, int Tq, int Tk,
+                  int dh, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, uint64_t seed, int dtype16, hipStream_t s);
+int attn_long_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* out, const void* dout, const float* lse,
+                  void* dq, void* dk, void* dv, float* delta, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo,
+                  int lddq, int lddk, int lddv, float scale, float drop_p, uint64_t seed, int dtype16, hipStream_t s);
 
 extern "C" int vmc_attention_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, void* out,
                                  float* lse, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo,
@@ -915,6 +931,10 @@ extern "C" int vmc_attention_fwd(const void* q, const void* k, const void* v, co
     if (dtype16 == VMC_F16) return launch_small<F16>(q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p, dropout_seed, (hipStream_t)stream);
     return VMC_E_DTYPE;
   }
+  if ((dh == 64 || dh == 96) && (ldo % 4) == 0 && ((uintptr_t)out & 7) == 0)   // longer sequences: tiled MFMA kernel
+    return attn_long_fwd(q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p, dropout_seed, dtype16,
+                         (hipStream_t)stream);
+  if ((rc = check_scalar_len(Tq, Tk))) return rc;
   dim3 grid(B * H * Tq);
   if (dtype16 == VMC_BF16)
     hipLaunchKernelGGL(attn_generic_fwd<BF16>, grid, dim3(64), 0, (hipStream_t)stream, (const uint16_t*)q, (const uint16_t*)k,
@@ -955,7 +975,11 @@ extern "C" int vmc_attention_bwd(const void* q, const void* k, const void* v, co
                         : launch_bwd_mfma<F16, 96>(q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, dropout_p, dropout_seed, st);
       return VMC_E_DTYPE;
     }
+    if ((((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7) == 0 && ((uintptr_t)out & 15) == 0)   // tiled MFMA kernels
+      return attn_long_bwd(q, k, v, key_mask, out, dout, lse, dq, dk, dv, (float*)workspace, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, lddq,
+                           lddk, lddv, scale, dropout_p, dropout_seed, dtype16, (hipStream_t)stream);
   }
+  if ((rc = check_scalar_len(Tq, Tk))) return rc;
   float* delta = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
 #define VMC_LAUNCH_BWD(TT)                                                                                                   \
