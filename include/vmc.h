@@ -150,8 +150,9 @@ int vmc_linear_wgrad_tn_group(const vmc_wgrad_tn_problem* probs, int n, int dtyp
  * state): VMC_GEMM_TWOSTAGE = two-stage tiles only, VMC_GEMM_DEFAULT = what vmc_linear does (8-phase 256x256 kernel; the
  * tile rows of a small last partial round handed to the small-tile kernel in a second launch; whole-tile problems with a
  * bias and a 16-bit output walk their tiles in a persistent workgroup per CU that prefetches the next tile's operands),
- * VMC_GEMM_NO_TAIL_SPLIT = the same without that split, VMC_GEMM_PERSISTENT = the persistent walk for every eligible
- * epilogue, VMC_GEMM_ONE_TILE = never persistent (one tile per workgroup).  Results are identical bit for bit across them. */
+ * VMC_GEMM_NO_TAIL_SPLIT = the same without that split, VMC_GEMM_PERSISTENT = the same as VMC_GEMM_DEFAULT (kept for the
+ * ABI), VMC_GEMM_ONE_TILE = never persistent (one tile per workgroup).  Results are identical bit for bit across them.
+ * The routing of every variant is vimo_clip_amd/csrc/gemm_route.h. */
 enum { VMC_GEMM_TWOSTAGE = 0, VMC_GEMM_DEFAULT = 1, VMC_GEMM_NO_TAIL_SPLIT = 2, VMC_GEMM_PERSISTENT = 3, VMC_GEMM_ONE_TILE = 4,
        VMC_GEMM_MFMA32 = 5, /* the persistent walk on v_mfma_f32_32x32x16 fragments (bias / QuickGELU / bias-free epilogues); the
                                k-steps are summed 16 at a time, so the last bit may differ from the other variants */

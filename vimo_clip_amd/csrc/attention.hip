@@ -225,12 +225,8 @@ template <typename T, int NT, int NC = 0, int NW = 4, bool REREAD = false, bool 
 static int launch_vit(const VitOperands& a, void* out, float* lse, int F, int N, int H, hipStream_t stream, int stagger = 0) {
   auto kern = attn_vit_kernel<T, NT, NC, NW, REREAD, PERSIST>;
   constexpr int LDS = 16 * NT * 128 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, LDS, kern)) return rc;
   const int grid = PERSIST ? (F * H < 512 ? F * H : 512) : F * H;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), LDS, stream, a.q, a.k, a.v, (uint16_t*)out, lse, N, a.NQ, H, a.ldq, a.ldkv, 0.125f, F * H,
                      stagger);

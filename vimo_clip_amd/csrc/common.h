@@ -24,6 +24,19 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
     if (e_ != hipSuccess) return (int)e_;           \
   } while (0)
 
+// Raise the dynamic-LDS limit of `kernels` to `bytes` once per process: `done` is the caller's flag, one per kernel instantiation
+// (a `static bool` beside the launch).  Several kernels (the dtypes of one launcher) are set together.
+template <typename... K>
+static inline int set_max_lds(bool& done, int bytes, K... kernels) {
+  if (done) return 0;
+  for (const void* k : {(const void*)kernels...}) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+  }
+  done = true;
+  return 0;
+}
+
 // ---- 16-bit element traits ---------------------------------------------------------------------
 struct BF16 {
   static constexpr int id = VMC_BF16;

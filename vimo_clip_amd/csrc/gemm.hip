@@ -364,12 +364,8 @@ static int launch_cfg(GemmArgs& g, hipStream_t stream) {
   constexpr int LDS = KS * NS * Cfg::STAGE > XCH ? KS * NS * Cfg::STAGE : XCH;
   static_assert(LDS <= 160 * 1024, "LDS");
   if (KS > 1 && g.k_slices > 1) return VMC_E_ARG;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, LDS, kern)) return rc;
   g.tiles_m = (g.M + Cfg::BM - 1) / Cfg::BM;
   g.tiles_n = (g.N + Cfg::BN - 1) / Cfg::BN;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n, g.k_slices), dim3(Cfg::NT * KS), LDS, stream, g);
@@ -377,165 +373,88 @@ static int launch_cfg(GemmArgs& g, hipStream_t stream) {
   return 0;
 }
 
-template <typename T, int ACT>
-static int launch_shape(GemmArgs& g, hipStream_t stream) {
-  // Tile choice: the 256x256 tile needs >= ~1 tile per CU to pay; smaller problems take smaller tiles
-  // so the grid still covers the 256 CUs (TFAM/head GEMMs have M = B*16 or B rows).
-  const long t256 = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
-  const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-  if constexpr (ACT == VMC_ACT_NONE) {      // builder A/B switch for the mid-size regime (profiles/README.md round 3)
-    static const int force = getenv("VMC_GEMM_CFG") ? atoi(getenv("VMC_GEMM_CFG")) : 0;
-    switch (force) {
-      case 1: return launch_cfg<T, ACT, 4, 2, 2, 3>(g, stream);      // 128 x 128, 3-stage ring
-      case 2: return launch_cfg<T, ACT, 4, 2, 2, 4>(g, stream);      // 128 x 128, 4-stage ring
-      case 3: return launch_cfg<T, ACT, 4, 2, 1, 4>(g, stream);      // 128 x 64, 4-stage ring
-      case 4: return launch_cfg<T, ACT, 2, 2, 2, 4>(g, stream);      // 64 x 128, 4-stage ring
-      case 5: return launch_cfg<T, ACT, 2, 2, 1, 4>(g, stream);      // 64 x 64, 4-stage ring
-      case 6: return launch_cfg<T, ACT, 4, 2, 2>(g, stream);         // 128 x 128, two stages (today's mid-size kernel)
-      case 7: return launch_cfg<T, ACT, 4, 2, 1, 6>(g, stream);      // 128 x 64, 6-stage ring
-      case 8: return launch_cfg<T, ACT, 2, 2, 2, 6>(g, stream);      // 64 x 128, 6-stage ring
-      case 9: return launch_cfg<T, ACT, 8, 2, 2>(g, stream);         // 256 x 128, two stages
-      case 10: return launch_cfg<T, ACT, 8, 2, 2, 3>(g, stream);     // 256 x 128, 3-stage ring
-      case 11: return launch_cfg<T, ACT, 4, 2, 4>(g, stream);        // 128 x 256, two stages
-      default: break;
-    }
-  }
-  if (t256 >= 192) return launch_cfg<T, ACT, 8, 2, 4>(g, stream);
-  if (t128 >= 128) return launch_cfg<T, ACT, 4, 2, 2>(g, stream);
-  // 64x64 tiles: latency-bound -> 4-stage ring.  A workgroup streams its (BM + 64) x K operand bytes at the ~70 GB/s one CU pulls
-  // from L2, so a long K chain on few workgroups is bound by that: when 64-row tiles give at most 128 workgroups (the 256-row tail
-  // of c_proj: 4 x 16), 32-row tiles put twice as many CUs on it (same per-row arithmetic and K order: same bits; 27.3 -> 21.8 us at
-  // K = 4096, 9.6 -> 7.9 us at K = 1024; 16-row single-wave tiles were slower again: 25.5 / 8.8 us).
-  // K >= 1024 on at most one workgroup per CU is ONE tile's dependent K chain: K-slice groups inside the workgroup (gemm_kernel's KS)
-  // shorten it.  Measured on the encoder's 256-row tails (us, KS = 1 -> routed): out_proj 8.5 -> 6.7 and c_proj (K = 4096) 22.8 -> 15.4
-  // with four groups on 3-stage rings over 32-row tiles; qkv 10.6 -> 8.4 and c_fc 11.2 -> 9.6 with two groups on 4-stage rings over 64^2
-  // tiles; two groups / four stages on the 32-row tiles and two groups / three stages on 64^2 were slower (7.9 / 20.4, 8.7 / 9.7);
-  // 128 x 768 x 2048 (TFAM ffn.3 at B = 8, per-op path) 12.5 -> 8.2; encoder step 40.42 -> 40.07 ms (+0.9 %).  NOT routed by default
-  // (VMC_GEMM_KS=1 turns it on): the groups sum the K tiles in another order than the persistent kernel, so a row's bits would depend
-  // on whether it falls into a GEMM's 256-row tail -- the encoder's outputs are bit-identical under any batch split today
-  // (tests/test_gpu_encoder.py), and 0.9 % does not buy that back.
-  static const bool ks_on = getenv("VMC_GEMM_KS") && atoi(getenv("VMC_GEMM_KS")) != 0;
-  const long t64 = (long)((g.M + 63) / 64) * ((g.N + 63) / 64);
-  // K tiles per barrier (gemm_kernel's U; same K order, same bits).  Measured on the encoder's 256-row tails and the TFAM small-batch
-  // shapes (us, U = 1 -> 4 on an 8-slot ring): 10.5 -> 9.9 (qkv), 7.8 -> 7.0, 8.5 -> 7.7 (out_proj), 22.7 -> 20.1 (c_proj, K = 4096),
-  // 11.1 = 11.1 (c_fc), 128 x 768 x 2048 12.4 -> 10.8; U = 2 on six slots: no gain.  An 8-slot ring of 64^2 tiles is 128 KiB (one
-  // workgroup per CU), so only problems of at most one workgroup per CU take it.  VMC_GEMM_U=1 turns it off (builder A/B switch).
-  static const int mt_sw = getenv("VMC_GEMM_U") ? atoi(getenv("VMC_GEMM_U")) : 4;
-  const bool u_ok = g.k_slices == 1 && g.K >= 512 && t64 <= 256;
-  if (t64 <= 128 && g.K >= 1024) {
-    if (ks_on && g.k_slices == 1) return launch_cfg<T, ACT, 1, 2, 1, 3, 4>(g, stream);
-    if (mt_sw == 2 && u_ok && (g.K / 64) % 2 == 0) return launch_cfg<T, ACT, 1, 2, 1, 6, 1, 2>(g, stream);
-    if (mt_sw == 4 && u_ok && (g.K / 64) % 4 == 0) return launch_cfg<T, ACT, 1, 2, 1, 8, 1, 4>(g, stream);
-    return launch_cfg<T, ACT, 1, 2, 1, 4>(g, stream);
-  }
-  if (ks_on && g.K >= 1024 && g.k_slices == 1 && t64 <= 256) return launch_cfg<T, ACT, 2, 2, 1, 4, 2>(g, stream);
-  if (mt_sw == 2 && u_ok && (g.K / 64) % 2 == 0) return launch_cfg<T, ACT, 2, 2, 1, 6, 1, 2>(g, stream);
-  if (mt_sw == 4 && u_ok && (g.K / 64) % 4 == 0) return launch_cfg<T, ACT, 2, 2, 1, 8, 1, 4>(g, stream);
-  return launch_cfg<T, ACT, 2, 2, 1, 4>(g, stream);
+// The tile configurations of gemm_route.h; the VMC_GEMM_CFG sweep exists for VMC_ACT_NONE only.
+template <typename T, int ACT, int I>
+static int launch_tile(GemmArgs& g, hipStream_t s) {
+  constexpr GemmTileCfg c = kGemmTileCfgs[I];
+  if constexpr (c.none_only && ACT != VMC_ACT_NONE) return VMC_E_ARG;
+  else return launch_cfg<T, ACT, c.mt, c.wm, c.wn, c.ns, c.ks, c.u>(g, s);
 }
-
+template <typename T, int ACT>
+static int tile_exec(GemmArgs& g, int cfg, hipStream_t s) {
+  static_assert(kGemmTileCfgCount == 19, "one case per entry of kGemmTileCfgs");
+  switch (cfg) {
+    case 0: return launch_tile<T, ACT, 0>(g, s); case 1: return launch_tile<T, ACT, 1>(g, s); case 2: return launch_tile<T, ACT, 2>(g, s);
+    case 3: return launch_tile<T, ACT, 3>(g, s); case 4: return launch_tile<T, ACT, 4>(g, s); case 5: return launch_tile<T, ACT, 5>(g, s);
+    case 6: return launch_tile<T, ACT, 6>(g, s); case 7: return launch_tile<T, ACT, 7>(g, s); case 8: return launch_tile<T, ACT, 8>(g, s);
+    case 9: return launch_tile<T, ACT, 9>(g, s); case 10: return launch_tile<T, ACT, 10>(g, s); case 11: return launch_tile<T, ACT, 11>(g, s);
+    case 12: return launch_tile<T, ACT, 12>(g, s); case 13: return launch_tile<T, ACT, 13>(g, s); case 14: return launch_tile<T, ACT, 14>(g, s);
+    case 15: return launch_tile<T, ACT, 15>(g, s); case 16: return launch_tile<T, ACT, 16>(g, s); case 17: return launch_tile<T, ACT, 17>(g, s);
+    case 18: return launch_tile<T, ACT, 18>(g, s);
+  }
+  return VMC_E_ARG;
+}
 template <typename T>
-static int launch_act(GemmArgs& g, int act, hipStream_t stream) {
+static int tile_exec_act(GemmArgs& g, int act, int cfg, hipStream_t s) {
   switch (act) {
-    case VMC_ACT_NONE: return launch_shape<T, VMC_ACT_NONE>(g, stream);
-    case VMC_ACT_QUICKGELU: return launch_shape<T, VMC_ACT_QUICKGELU>(g, stream);
-    case VMC_ACT_GELU_ERF: return launch_shape<T, VMC_ACT_GELU_ERF>(g, stream);
-    case VMC_ACT_RELU: return launch_shape<T, VMC_ACT_RELU>(g, stream);
+    case VMC_ACT_NONE: return tile_exec<T, VMC_ACT_NONE>(g, cfg, s);
+    case VMC_ACT_QUICKGELU: return tile_exec<T, VMC_ACT_QUICKGELU>(g, cfg, s);
+    case VMC_ACT_GELU_ERF: return tile_exec<T, VMC_ACT_GELU_ERF>(g, cfg, s);
+    case VMC_ACT_RELU: return tile_exec<T, VMC_ACT_RELU>(g, cfg, s);
   }
   return VMC_E_ARG;
 }
 
-static int linear_impl(const void* A, const void* W, const float* bias, const void* res, void* C, void* Z,
-                       int M, int N, int K, int lda, int ldw, int ldc, int ldres, int ldz,
-                       int act, float alpha, int out_dtype, int res_dtype, int out_row_group, int res_row_mod,
-                       int dtype16, int variant, void* stream);
+// validate -> route (gemm_route.h) -> launch every part of the plan on its rows
+static int linear_impl(const GemmProblem& p, int variant, void* stream) {
+  if (int rc = gemm_check(p, variant)) return rc;
+  const GemmOverrides& ov = gemm_overrides();
+  const GemmPlan plan = gemm_route(p, variant, ov);
+  GemmArgs g;
+  g.W = (const char*)p.W; g.bias = (const float*)p.bias;
+  g.N = p.N; g.K = p.K; g.lda = p.lda; g.ldw = p.ldw; g.ldc = p.ldc; g.ldres = p.ldres; g.ldz = p.ldz;
+  g.alpha = p.alpha; g.out_f32 = (p.out_dtype == VMC_F32); g.res_f32 = (p.res_dtype == VMC_F32);
+  g.out_row_group = p.out_row_group; g.res_row_mod = p.res_row_mod;
+  g.tiles_m = g.tiles_n = 0; g.variant = variant; g.walk_gc = ov.gc; g.k_slices = 1;
+  const hipStream_t s = (hipStream_t)stream;
+  for (int i = 0; i < plan.n; ++i) {
+    const GemmLaunch& l = plan.launch[i];
+    const size_t r0 = (size_t)l.row0;
+    g.M = l.rows;
+    g.A = (const char*)p.A + r0 * p.lda * 2;
+    g.C = (char*)p.C + r0 * p.ldc * (g.out_f32 ? 4 : 2);
+    g.res = p.res ? (const char*)p.res + r0 * p.ldres * (g.res_f32 ? 4 : 2) : nullptr;
+    g.zout = p.Z ? (char*)p.Z + r0 * p.ldz * 2 : nullptr;
+    const int rc = l.family != GEMM_TILE ? vmc_gemm8_launch(g, l, p.act, p.dtype16, s)
+                   : p.dtype16 == VMC_BF16 ? tile_exec_act<BF16>(g, p.act, l.cfg, s) : tile_exec_act<F16>(g, p.act, l.cfg, s);
+    if (rc) return rc;
+  }
+  return 0;
+}
 
 extern "C" int vmc_linear(const void* A, const void* W, const float* bias, const void* res, void* C,
                           int M, int N, int K, int lda, int ldw, int ldc, int ldres,
                           int act, float alpha, int out_dtype, int res_dtype, int out_row_group, int res_row_mod,
                           int dtype16, void* stream) {
-  return linear_impl(A, W, bias, res, C, nullptr, M, N, K, lda, ldw, ldc, ldres, 0, act, alpha, out_dtype, res_dtype, out_row_group,
-                     res_row_mod, dtype16, VMC_GEMM_DEFAULT, stream);
+  return linear_impl({A, W, bias, res, C, nullptr, M, N, K, lda, ldw, ldc, ldres, 0, act, alpha, out_dtype, res_dtype, out_row_group,
+                      res_row_mod, dtype16}, VMC_GEMM_DEFAULT, stream);
 }
 
 extern "C" int vmc_linear_variant(const void* A, const void* W, const float* bias, const void* res, void* C,
                                   int M, int N, int K, int lda, int ldw, int ldc, int ldres,
                                   int act, float alpha, int out_dtype, int res_dtype, int out_row_group, int res_row_mod,
                                   int dtype16, int variant, void* stream) {
-  if (variant < 0 || variant >= VMC_GEMM_VARIANTS) return VMC_E_ARG;
-  return linear_impl(A, W, bias, res, C, nullptr, M, N, K, lda, ldw, ldc, ldres, 0, act, alpha, out_dtype, res_dtype, out_row_group,
-                     res_row_mod, dtype16, variant, stream);
+  return linear_impl({A, W, bias, res, C, nullptr, M, N, K, lda, ldw, ldc, ldres, 0, act, alpha, out_dtype, res_dtype, out_row_group,
+                      res_row_mod, dtype16}, variant, stream);
 }
 
 extern "C" int vmc_linear_preact(const void* A, const void* W, const float* bias, const void* res, void* C, void* Z,
                                  int M, int N, int K, int lda, int ldw, int ldc, int ldres, int ldz,
                                  int act, float alpha, int out_dtype, int res_dtype, int out_row_group, int res_row_mod,
                                  int dtype16, void* stream) {
-  return linear_impl(A, W, bias, res, C, Z, M, N, K, lda, ldw, ldc, ldres, ldz, act, alpha, out_dtype, res_dtype, out_row_group,
-                     res_row_mod, dtype16, VMC_GEMM_DEFAULT, stream);
+  return linear_impl({A, W, bias, res, C, Z, M, N, K, lda, ldw, ldc, ldres, ldz, act, alpha, out_dtype, res_dtype, out_row_group,
+                      res_row_mod, dtype16}, VMC_GEMM_DEFAULT, stream);
 }
-
-static int linear_impl(const void* A, const void* W, const float* bias, const void* res, void* C, void* Z,
-                       int M, int N, int K, int lda, int ldw, int ldc, int ldres, int ldz,
-                       int act, float alpha, int out_dtype, int res_dtype, int out_row_group, int res_row_mod,
-                       int dtype16, int variant, void* stream) {
-  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return VMC_E_ARG;
-  if (Z && (ldz < N || (ldz % 4) || ((uintptr_t)Z & 15) || out_row_group)) return VMC_E_ARG;
-  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
-  if (K % 64 != 0 || N % 4 != 0) return VMC_E_SHAPE;
-  if (lda % 8 || ldw % 8 || ldc % 4 || (res && (ldres % 4))) return VMC_E_ALIGN;
-  if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)res | (uintptr_t)bias) & 15) return VMC_E_ALIGN;
-  if (lda < K || ldw < K || ldc < N) return VMC_E_ARG;
-  if (out_dtype != VMC_F32 && out_dtype != dtype16) return VMC_E_DTYPE;
-  if (res && res_dtype != VMC_F32 && res_dtype != dtype16) return VMC_E_DTYPE;
-  GemmArgs g;
-  g.A = (const char*)A; g.W = (const char*)W; g.bias = bias; g.res = (const char*)res; g.C = (char*)C;
-  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldres = ldres;
-  g.alpha = alpha; g.out_f32 = (out_dtype == VMC_F32); g.res_f32 = (res_dtype == VMC_F32);
-  g.out_row_group = out_row_group; g.res_row_mod = res_row_mod;
-  g.tiles_m = g.tiles_n = 0;
-  g.k_slices = 1;
-  g.zout = (char*)Z; g.ldz = ldz;
-  // large problems with an even K-tile count take the 8-phase 256x256 kernel (gemm8.hip);
-  // variant VMC_GEMM_TWOSTAGE forces the two-stage kernels (A/B measurements through vmc_linear_variant).
-  g.variant = variant;
-  const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  // Between 129 and 191 tiles of 256x256 the 128x128 kernel would need a second round of its 512 resident workgroups (t128 > 512)
-  // while the 8-phase kernel still finishes in one: M = 4096, N = 2304, K = 768 (TFAM qkv at 256 clips) 31.6 -> 21.2 us; at <= 128
-  // tiles the two are equal (20.8 / 20.0 us at 96 tiles) and below 96 the small tiles win (profiles/README.md, round 2).
-  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128);
-  const bool big = t256 >= 192 || (t256 > 128 && t128 > 512);
-  if (variant != VMC_GEMM_TWOSTAGE && big && (K % 128) == 0) {
-    // Round quantisation: T tiles on 256 CUs cost ceil(T/256) tile-times.  When the last, partial round holds only a few
-    // tiles (ViT-L/14: 257 x tn tiles -> tn tiles in a round of their own: +25 % at tn = 4; student ViT-B/32: 100 x 3 tiles ->
-    // 44 tiles in a second round), the tile rows that do not fit the full rounds go to the small-tile kernels, which spread
-    // them over the whole chip, in a second launch.
-    const int tm = (M + 255) / 256, tn = (N + 255) / 256;
-    // whole tile rows that fit in the full rounds (a last main round may leave up to tn - 1 CUs idle); the rest is the tail
-    const int rounds = (int)(t256 / 256);
-    const int main_rows = rounds > 0 ? (rounds * 256) / tn : 0;
-    const long tail = (long)(tm - main_rows) * tn;              // tiles handed to the small-tile kernel
-    if (variant != VMC_GEMM_NO_TAIL_SPLIT && !out_row_group && !res_row_mod && main_rows > 0 && main_rows < tm && t256 % 256 != 0 &&
-        tail <= (rounds >= 2 ? 64 : 96)) {
-      const int m_main = main_rows * 256;
-      GemmArgs t = g;
-      g.M = m_main;
-      int rc = vmc_gemm8_launch(g, act, dtype16, (hipStream_t)stream);
-      if (rc) return rc;
-      t.M = M - m_main;
-      t.A += (size_t)m_main * lda * 2;
-      t.C += (size_t)m_main * ldc * (t.out_f32 ? 4 : 2);
-      if (t.res) t.res += (size_t)m_main * ldres * (t.res_f32 ? 4 : 2);
-      if (t.zout) t.zout += (size_t)m_main * ldz * 2;
-      if (dtype16 == VMC_BF16) return launch_act<BF16>(t, act, (hipStream_t)stream);
-      return launch_act<F16>(t, act, (hipStream_t)stream);
-    }
-    return vmc_gemm8_launch(g, act, dtype16, (hipStream_t)stream);
-  }
-  if (dtype16 == VMC_BF16) return launch_act<BF16>(g, act, (hipStream_t)stream);
-  return launch_act<F16>(g, act, (hipStream_t)stream);
-}
-
 
 // out[w] = sum_p partial[p*W + w], float4 per thread, fixed order (deterministic)
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restrict__ partial, float* __restrict__ out, int P, size_t W4) {
@@ -549,23 +468,10 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
   }
 }
 
-static int splitk_slices(int M, int N, int K) {
-  const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-  int slices = (768 + tiles - 1) / tiles;              // ~3 workgroups per CU
-  const int nkt = K / 64;
-  if (slices > nkt / 4) slices = nkt / 4;              // at least 4 K tiles per slice
-  if (slices < 1) slices = 1;
-  const int per = (nkt + slices - 1) / slices;         // the kernel's per-slice tile count ...
-  return (nkt + per - 1) / per;                        // ... and no empty trailing slice (its slab would stay unwritten)
-}
-
 // Weight-gradient GEMM (K8): C[M,N] (f32, contiguous) = A[M,K] @ W[N,K]^T with a long contraction (K = tokens) and a
 // small output: 128x128 tiles x K slices so that the grid covers the chip; every slice writes a partial slab into the
 // workspace and a second kernel sums the slabs in a fixed order (deterministic, no atomics).
-extern "C" size_t vmc_linear_splitk_workspace_bytes(int M, int N, int K) {
-  const int s = splitk_slices(M, N, K);
-  return s > 1 ? (size_t)s * M * N * sizeof(float) : 0;
-}
+extern "C" size_t vmc_linear_splitk_workspace_bytes(int M, int N, int K) { return splitk_workspace_bytes(M, N, K); }
 
 extern "C" int vmc_linear_splitk_f32(const void* A, const void* W, float* C, int M, int N, int K, int lda, int ldw, void* workspace,
                                      size_t workspace_bytes, int dtype16, void* stream) {
@@ -574,7 +480,7 @@ extern "C" int vmc_linear_splitk_f32(const void* A, const void* W, float* C, int
   if (lda % 8 || ldw % 8) return VMC_E_ALIGN;
   if (((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)workspace) & 15) return VMC_E_ALIGN;
   const int slices = splitk_slices(M, N, K);
-  if (slices > 1 && (!workspace || workspace_bytes < vmc_linear_splitk_workspace_bytes(M, N, K))) return VMC_E_ARG;
+  if (slices > 1 && (!workspace || workspace_bytes < splitk_workspace_bytes(M, N, K))) return VMC_E_ARG;
   GemmArgs g;
   g.A = (const char*)A; g.W = (const char*)W; g.bias = nullptr; g.res = nullptr;
   g.C = slices > 1 ? (char*)workspace : (char*)C;
@@ -584,13 +490,11 @@ extern "C" int vmc_linear_splitk_f32(const void* A, const void* W, float* C, int
   g.variant = VMC_GEMM_DEFAULT;
   g.zout = nullptr; g.ldz = 0;
   hipStream_t s = (hipStream_t)stream;
-  int rc = dtype16 == VMC_BF16 ? launch_cfg<BF16, VMC_ACT_NONE, 4, 2, 2>(g, s)
-           : dtype16 == VMC_F16 ? launch_cfg<F16, VMC_ACT_NONE, 4, 2, 2>(g, s) : VMC_E_DTYPE;
+  int rc = dtype16 == VMC_BF16 ? tile_exec<BF16, VMC_ACT_NONE>(g, kGemmSplitKCfg, s)
+           : dtype16 == VMC_F16 ? tile_exec<F16, VMC_ACT_NONE>(g, kGemmSplitKCfg, s) : VMC_E_DTYPE;
   if (rc || slices == 1) return rc;
   const size_t W4 = (size_t)M * N / 4;
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid_for(W4, 256)), dim3(256), 0, s, (const float*)workspace, C, slices, W4);
   VMC_CHECK_LAUNCH();
   return 0;
 }
-
-

@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(512, 2) gemm8_kernel(const GemmArgs g) {
 //    Conversions and stores overlap the partner's MFMAs; no accumulator is live twice and none is zeroed on the critical path.
 // Operand addresses are buffer offsets: voffset = the lane's fixed offset, soffset = the panel (SGPR), so walking tiles costs no
 // VGPRs and no 64-bit per-lane pointer exists (with global_load_lds hipcc sometimes materialises four of them and spills).
-// Whole interior tiles, 16-bit output with bias, K >= 256 only (the launcher checks).
+// Whole interior tiles, 16-bit output with bias, K >= 256 only (gemm_route.h checks).
 struct G8Panel { uint32_t a, b; };   // byte offsets of the A / W panels of one K tile inside their operands (uniform)
 
 __device__ __forceinline__ void g8p_stage(const __amdgpu_buffer_rsrc_t rs, char* slot, uint32_t panel, const uint32_t (&off)[2],
@@ -816,12 +816,8 @@ __global__ void __launch_bounds__(512, 2) gemm8p32_kernel(const GemmArgs g) {
 template <typename T, int ACT>
 static int g8_launch(GemmArgs& g, hipStream_t stream) {
   auto kern = gemm8_kernel<T, ACT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * G8_SLOT);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, 8 * G8_SLOT, kern)) return rc;
   g.tiles_m = (g.M + 255) / 256;
   g.tiles_n = (g.N + 255) / 256;
   hipLaunchKernelGGL(kern, dim3(g.tiles_m * g.tiles_n), dim3(512), 8 * G8_SLOT, stream, g);
@@ -829,93 +825,41 @@ static int g8_launch(GemmArgs& g, hipStream_t stream) {
   return 0;
 }
 
-template <typename T, int ACT, bool BIAS, bool ZOUT>
-static int g8p32_launch(GemmArgs& g, hipStream_t stream) {
-  auto kern = gemm8p32_kernel<T, ACT, BIAS, ZOUT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * G8_SLOT + 2048);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  g.tiles_m = g.M / 256;
-  g.tiles_n = g.N / 256;
-  hipLaunchKernelGGL(kern, dim3(256), dim3(512), 8 * G8_SLOT + 2048, stream, g);
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T, int ACT, bool BIAS, bool ZOUT>
+// The persistent walks of gemm_route.h's kGemm8pInsts: one workgroup per CU over whole 256x256 tiles.
+template <typename T, int I>
 static int g8p_launch(GemmArgs& g, hipStream_t stream) {
-  auto kern = gemm8p_kernel<T, ACT, BIAS, ZOUT>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * G8_SLOT + 2048);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  constexpr Gemm8pInst P = kGemm8pInsts[I];
+  void (*kern)(const GemmArgs);
+  if constexpr (P.mfma32) kern = gemm8p32_kernel<T, P.act, P.bias, P.zout>;
+  else kern = gemm8p_kernel<T, P.act, P.bias, P.zout>;
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, 8 * G8_SLOT + 2048, kern)) return rc;
   g.tiles_m = g.M / 256;
   g.tiles_n = g.N / 256;
   hipLaunchKernelGGL(kern, dim3(256), dim3(512), 8 * G8_SLOT + 2048, stream, g);
   VMC_CHECK_LAUNCH();
   return 0;
-}
-
-// The persistent kernel takes problems made of whole 256x256 tiles (at least 192 of them, at least two K iterations) with a
-// plain 16-bit output: the encoders' qkv / out_proj / c_fc / c_proj (bias), the same with the pre-activation side output of
-// training (QuickGELU c_fc), and the bias-free input-gradient GEMMs.  Everything else -- fp32 residual epilogue, row remaps,
-// other activation / side-output combinations -- runs one tile per workgroup.
-static bool g8p_eligible(const GemmArgs& g) {
-  if ((g.M & 255) || (g.N & 255) || (long)(g.M / 256) * (g.N / 256) < 192 || g.K < 256) return false;
-  if ((size_t)g.M * g.lda * 2 >= (1ull << 31) || (size_t)g.N * g.ldw * 2 >= (1ull << 31)) return false;   // buffer descriptors / 32-bit offsets
-  if ((size_t)255 * g.ldc * 2 + 512 >= (1ull << 31) || (g.zout && g.ldz != g.ldc)) return false;
-  return g8_epi_kind(g) == G8_EPI_STORE16;
-}
-
-template <typename T, int ACT>
-static int g8_pick(GemmArgs& g, hipStream_t s) {
-  // instantiated combinations only (each is a ~2000-instruction kernel); erf-GELU spills in the persistent kernel, and scratch
-  // accesses count in vmcnt -> one-tile kernel
-  if (g.variant != VMC_GEMM_ONE_TILE && g8p_eligible(g)) {
-    const bool b = g.bias != nullptr, z = g.zout != nullptr;
-    static const bool env32 = getenv("VMC_GEMM_MFMA32") && atoi(getenv("VMC_GEMM_MFMA32")) != 0;      // builder A/B switch
-    if ((env32 || g.variant == VMC_GEMM_MFMA32) && !z) {
-      if constexpr (ACT == VMC_ACT_NONE) {
-        if (b) return g8p32_launch<T, ACT, true, false>(g, s);
-        return g8p32_launch<T, ACT, false, false>(g, s);
-      } else if constexpr (ACT == VMC_ACT_QUICKGELU) {
-        if (b) return g8p32_launch<T, ACT, true, false>(g, s);
-      }
-    }
-    if constexpr (ACT == VMC_ACT_NONE) {
-      if (b && !z) return g8p_launch<T, ACT, true, false>(g, s);
-      if (!b && !z) return g8p_launch<T, ACT, false, false>(g, s);
-    } else if constexpr (ACT == VMC_ACT_QUICKGELU) {
-      if (b && !z) return g8p_launch<T, ACT, true, false>(g, s);
-      if (b && z) return g8p_launch<T, ACT, true, true>(g, s);
-    } else if constexpr (ACT == VMC_ACT_RELU) {
-      if (b && !z) return g8p_launch<T, ACT, true, false>(g, s);
-    }
-  }
-  return g8_launch<T, ACT>(g, s);
 }
 
 template <typename T>
-static int g8_act(GemmArgs& g, int act, hipStream_t s) {
+static int g8_exec(GemmArgs& g, const GemmLaunch& l, int act, hipStream_t s) {
+  static_assert(kGemm8pInstCount == 8, "one case per entry of kGemm8pInsts");
+  if (l.family == GEMM_8P) {
+    switch (l.cfg) {
+      case 0: return g8p_launch<T, 0>(g, s); case 1: return g8p_launch<T, 1>(g, s); case 2: return g8p_launch<T, 2>(g, s); case 3: return g8p_launch<T, 3>(g, s);
+      case 4: return g8p_launch<T, 4>(g, s); case 5: return g8p_launch<T, 5>(g, s); case 6: return g8p_launch<T, 6>(g, s); case 7: return g8p_launch<T, 7>(g, s);
+    }
+    return VMC_E_ARG;
+  }
   switch (act) {
-    case VMC_ACT_NONE: return g8_pick<T, VMC_ACT_NONE>(g, s);
-    case VMC_ACT_QUICKGELU: return g8_pick<T, VMC_ACT_QUICKGELU>(g, s);
-    case VMC_ACT_GELU_ERF: return g8_pick<T, VMC_ACT_GELU_ERF>(g, s);
-    case VMC_ACT_RELU: return g8_pick<T, VMC_ACT_RELU>(g, s);
+    case VMC_ACT_NONE: return g8_launch<T, VMC_ACT_NONE>(g, s);
+    case VMC_ACT_QUICKGELU: return g8_launch<T, VMC_ACT_QUICKGELU>(g, s);
+    case VMC_ACT_GELU_ERF: return g8_launch<T, VMC_ACT_GELU_ERF>(g, s);
+    case VMC_ACT_RELU: return g8_launch<T, VMC_ACT_RELU>(g, s);
   }
   return VMC_E_ARG;
 }
 
-int vmc_gemm8_launch(GemmArgs& g, int act, int dtype16, hipStream_t stream) {
-  if ((g.K & 127) != 0) return VMC_E_SHAPE;  // K tiles are consumed in pairs
-  static const int walk_gc = getenv("VMC_GEMM_GC") ? atoi(getenv("VMC_GEMM_GC")) : 0;      // builder A/B switch (profiles/README.md)
-  g.walk_gc = walk_gc;
-  if (dtype16 == VMC_BF16) return g8_act<BF16>(g, act, stream);
-  if (dtype16 == VMC_F16) return g8_act<F16>(g, act, stream);
-  return VMC_E_DTYPE;
+int vmc_gemm8_launch(GemmArgs& g, const GemmLaunch& l, int act, int dtype16, hipStream_t stream) {
+  return dtype16 == VMC_BF16 ? g8_exec<BF16>(g, l, act, stream) : dtype16 == VMC_F16 ? g8_exec<F16>(g, l, act, stream) : VMC_E_DTYPE;
 }

@@ -69,74 +69,35 @@ __global__ void __launch_bounds__(256) tn_reduce_kernel(const float* __restrict_
   ((float4*)out)[i] = s;
 }
 
-static int tn_slices(int M, int N, int K) {
-  const int tiles = ((N + 255) / 256) * ((K + 127) / 128);
-  // one workgroup per CU (144 KiB of LDS): aim at whole rounds of 256 workgroups -- one round when the tiles allow it
-  // (fewer, longer slices: half the slab traffic of the reduce), two when a single round would leave > 1/4 of the chip idle
-  // (measured against ceil(512 / tiles) slices: 62 vs 83 us at 768x768, 164 vs 206 us at 3072x768, M = 25 600)
-  int slices = 256 / tiles;
-  if (slices >= 1 && tiles * slices < 192) slices = 512 / tiles;
-  const int steps = (M + 63) / 64;
-  if (slices > steps / 4) slices = steps / 4;
-  if (slices < 1) slices = 1;
-  const int per = (steps + slices - 1) / slices;
-  return (steps + per - 1) / per;                      // no empty trailing slice
-}
-// Large problems made of whole 128-token pairs go to the 256 x 256 tile (gemm_tn256.hip); VMC_TN256=0 is the builder's A/B switch.
-static bool tn_use256(int M, int N, int K, int lddy, int ldx) {
-  static const bool on = !(getenv("VMC_TN256") && atoi(getenv("VMC_TN256")) == 0);
-  return on && vmc_tn256_eligible(M, N, K, lddy, ldx);
-}
-extern "C" size_t vmc_linear_wgrad_tn_workspace_bytes(int M, int N, int K) {
-  int s = tn_slices(M, N, K);
-  if (vmc_tn256_eligible(M, N, K, N, K)) {     // the leading dimensions are not known here: room for whichever kernel the call takes
-    int s2, per;
-    vmc_tn256_slices(M, N, K, &s2, &per);
-    if (s2 > s) s = s2;
-  }
-  return s > 1 ? (size_t)s * ((size_t)N * K + N) * sizeof(float) : 0;      // weight slabs, then bias slabs
-}
+extern "C" size_t vmc_linear_wgrad_tn_workspace_bytes(int M, int N, int K) { return tn_workspace_bytes(M, N, K, gemm_overrides()); }
 extern "C" int vmc_linear_wgrad_bias_tn(const void* dY, const void* X, float* C, float* dbias, int M, int N, int K, int lddy, int ldx,
                                         void* workspace, size_t workspace_bytes, int dtype16, void* stream) {
   if (!dY || !X || !C || M <= 0 || N <= 0 || K <= 0) return VMC_E_ARG;
   if ((N % 8) || (K % 8)) return VMC_E_SHAPE;
   if ((lddy % 8) || (ldx % 8)) return VMC_E_ALIGN;
   if (((uintptr_t)dY | (uintptr_t)X | (uintptr_t)C | (uintptr_t)workspace | (uintptr_t)dbias) & 15) return VMC_E_ALIGN;
-  const bool big = tn_use256(M, N, K, lddy, ldx);
-  int slices = tn_slices(M, N, K), pairs_per_slice = 0;
-  if (big) vmc_tn256_slices(M, N, K, &slices, &pairs_per_slice);
-  if (slices > 1 && (!workspace || workspace_bytes < (size_t)slices * ((size_t)N * K + N) * sizeof(float))) return VMC_E_ARG;
+  const TnPlan plan = tn_route(M, N, K, lddy, ldx, gemm_overrides());
+  const int slices = plan.slices;
+  if (slices > 1 && (!workspace || workspace_bytes < tn_slab_bytes(slices, N, K))) return VMC_E_ARG;
   float* dst = slices > 1 ? (float*)workspace : C;
   float* bdst = !dbias ? nullptr : (slices > 1 ? (float*)workspace + (size_t)slices * N * K : dbias);
   hipStream_t s = (hipStream_t)stream;
-  if (big) {
-    const int rc = vmc_tn256_launch(dY, X, dst, bdst, M, N, K, lddy, ldx, slices, pairs_per_slice, dtype16, s);
-    if (rc) return rc;
-    if (slices > 1) {
-      const size_t n4 = (size_t)N * K / 4, n4b = dbias ? (size_t)N / 4 : 0;
-      hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n4 + n4b + 255) / 256)), dim3(256), 0, s, (const float*)workspace, C, slices, n4,
-                         (const float*)bdst, dbias, n4b);
-      VMC_CHECK_LAUNCH();
-    }
-    return 0;
+  if (plan.k256) {
+    if (const int rc = vmc_tn256_launch(dY, X, dst, bdst, M, N, K, lddy, ldx, slices, plan.pairs_per_slice, dtype16, s)) return rc;
+  } else {
+    const int tiles_k = (K + 127) / 128, tiles_n = (N + 255) / 256;
+    dim3 grid(tiles_n * tiles_k * slices);
+    const size_t lds = (size_t)TN_STAGES * TN_STAGE;
+    static bool lds_set = false;
+    if (int rc = set_max_lds(lds_set, (int)lds, gemm_tn_kernel<BF16>, gemm_tn_kernel<F16>)) return rc;
+    if (dtype16 == VMC_BF16)
+      hipLaunchKernelGGL(gemm_tn_kernel<BF16>, grid, dim3(512), lds, s, (const uint16_t*)dY, (const uint16_t*)X, dst, bdst, M, N, K, lddy, ldx, tiles_k, tiles_n, slices);
+    else if (dtype16 == VMC_F16)
+      hipLaunchKernelGGL(gemm_tn_kernel<F16>, grid, dim3(512), lds, s, (const uint16_t*)dY, (const uint16_t*)X, dst, bdst, M, N, K, lddy, ldx, tiles_k, tiles_n, slices);
+    else
+      return VMC_E_DTYPE;
+    VMC_CHECK_LAUNCH();
   }
-  const int tiles_k = (K + 127) / 128, tiles_n = (N + 255) / 256;
-  dim3 grid(tiles_n * tiles_k * slices);
-  const size_t lds = (size_t)TN_STAGES * TN_STAGE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(gemm_tn_kernel<BF16>, grid, dim3(512), lds, s, (const uint16_t*)dY, (const uint16_t*)X, dst, bdst, M, N, K, lddy, ldx, tiles_k, tiles_n, slices);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(gemm_tn_kernel<F16>, grid, dim3(512), lds, s, (const uint16_t*)dY, (const uint16_t*)X, dst, bdst, M, N, K, lddy, ldx, tiles_k, tiles_n, slices);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
   if (slices > 1) {
     const size_t n4 = (size_t)N * K / 4, n4b = dbias ? (size_t)N / 4 : 0;
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)((n4 + n4b + 255) / 256)), dim3(256), 0, s, (const float*)workspace, C, slices, n4,

@@ -298,41 +298,13 @@ __global__ void __launch_bounds__(512, 2) gemm_tn256_group_kernel(const Tn256Gro
                      smem);
 }
 
-// ---- host side ----------------------------------------------------------------------------------------------------------------
-// Eligibility and slicing are shared with gemm_tn.hip through these two functions (declared in gemm_common.h).
-bool vmc_tn256_eligible(int M, int N, int K, int lddy, int ldx) {
-  if (M < 256 || (M & 127)) return false;                                    // whole stage pairs, no token tail
-  const long tiles = (long)((N + 255) / 256) * ((K + 255) / 256);
-  if (tiles < 16) return false;                                              // fewer: too many slabs for the reduce (768 x 768: 28)
-  if ((size_t)M * lddy * 2 >= (1ull << 31) || (size_t)M * ldx * 2 >= (1ull << 31)) return false;     // buffer descriptors
-  // short slices are all prologue and slab traffic (M = 4096, 512 x 2048: 16 slices of two pairs, 32 vs 27 us)
-  static const int min_pairs = getenv("VMC_TN256_MINPAIRS") ? atoi(getenv("VMC_TN256_MINPAIRS")) : 8;
-  int slices, per;
-  vmc_tn256_slices(M, N, K, &slices, &per);
-  return per >= min_pairs;
-}
-void vmc_tn256_slices(int M, int N, int K, int* slices, int* pairs_per_slice) {
-  const int tiles = ((N + 255) / 256) * ((K + 255) / 256), pairs = M / 128;
-  // one workgroup per CU (128 KiB of LDS): one round of at most 256 workgroups
-  int s = 256 / tiles;
-  if (s > pairs / 2) s = pairs / 2;
-  if (s < 1) s = 1;
-  const int per = (pairs + s - 1) / s;
-  *pairs_per_slice = per;
-  *slices = (pairs + per - 1) / per;                  // no empty trailing slice
-}
-
+// ---- host side (routing and slicing: tn_route in gemm_route.h) ------------------------------------------------------------
 int vmc_tn256_launch(const void* dY, const void* X, float* dst, float* bdst, int M, int N, int K, int lddy, int ldx, int slices,
                      int pairs_per_slice, int dtype16, hipStream_t s) {
   const int tiles_k = (K + 255) / 256, tiles_n = (N + 255) / 256;
   const size_t lds = 8 * T2_SLOT;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn256_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn256_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, (int)lds, gemm_tn256_kernel<BF16>, gemm_tn256_kernel<F16>)) return rc;
   dim3 grid(tiles_n * tiles_k * slices);
   if (dtype16 == VMC_BF16)
     hipLaunchKernelGGL(gemm_tn256_kernel<BF16>, grid, dim3(512), lds, s, (const uint16_t*)dY, (const uint16_t*)X, dst, bdst, M, N, K, lddy, ldx,
@@ -365,13 +337,8 @@ extern "C" int vmc_linear_wgrad_tn_group(const vmc_wgrad_tn_problem* probs, int 
   }
   g.tile0[n] = tiles;
   const size_t lds = 8 * T2_SLOT;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn256_group_kernel<BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn256_group_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_set = true;
-  }
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, (int)lds, gemm_tn256_group_kernel<BF16>, gemm_tn256_group_kernel<F16>)) return rc;
   if (dtype16 == VMC_BF16)
     hipLaunchKernelGGL(gemm_tn256_group_kernel<BF16>, dim3(tiles), dim3(512), lds, (hipStream_t)stream, g);
   else

@@ -971,16 +971,6 @@ constexpr size_t tf_lds_bytes(int cpb, int Tk) {
          (PRO == PRO_ATTN ? (size_t)((cpb - 1) * Tk + 16 * NKT) * KD * 2 + 1024 : 0);    // + one LDS-DMA piece of slack
 }
 
-template <typename K>
-int tf_set_lds(K kern, bool& done) {
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TF_LDS_MAX);
-    if (e != hipSuccess) return (int)e;
-    done = true;
-  }
-  return 0;
-}
-
 template <typename T, int BN, int PRO, int EPI, int KD, int DH, int QT, int NKT = 1, bool TR = false>
 int tf_launch(TfArgs& a, hipStream_t s) {
   const size_t lds = tf_lds_bytes<BN, PRO, KD, NKT>(a.cpb, a.Tk);
@@ -990,7 +980,7 @@ int tf_launch(TfArgs& a, hipStream_t s) {
   a.n_rb = (PRO == PRO_ATTN && a.parts > 1) ? a.B * a.parts : (a.M + a.rpb - 1) / a.rpb;
   auto kern = tf_gemm_kernel<T, BN, PRO, EPI, KD, DH, QT, NKT, TF_NW, TR>;
   static bool attr_done = false;                // per instantiation
-  if (int rc = tf_set_lds(kern, attr_done)) return rc;
+  if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
   hipLaunchKernelGGL(kern, dim3(a.n_tiles * a.n_rb), dim3(64 * TF_NW), lds, s, a);
   VMC_CHECK_LAUNCH();
   return 0;
@@ -1004,7 +994,7 @@ int tf_launch_pair(TfArgs& a, TfArgs& b, hipStream_t s) {
   b.n_tiles = (b.N + BN - 1) / BN; b.n_rb = (b.M + b.rpb - 1) / b.rpb;
   auto kern = tf_gemm_pair_kernel<T, BN, PRO, EPI, KD, TF_NW, TR>;
   static bool attr_done = false;
-  if (int rc = tf_set_lds(kern, attr_done)) return rc;
+  if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
   const int na = a.n_tiles * a.n_rb;
   hipLaunchKernelGGL(kern, dim3(na + b.n_tiles * b.n_rb), dim3(64 * TF_NW), lds, s, a, b, na);
   VMC_CHECK_LAUNCH();
@@ -1019,7 +1009,7 @@ int tf_launch_ring(TfArgs& a, hipStream_t s) {
   a.n_rb = (a.M + a.rpb - 1) / a.rpb;
   auto kern = tf_gemm_ring_kernel<T, BN, KC, NST, TR>;
   static bool attr_done = false;
-  if (int rc = tf_set_lds(kern, attr_done)) return rc;
+  if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
   hipLaunchKernelGGL(kern, dim3(a.n_tiles * a.n_rb), dim3(TF_NTH), lds, s, a);
   VMC_CHECK_LAUNCH();
   return 0;

@@ -660,7 +660,7 @@ int tr_wgrad_launch(const TrWgradGroup& g, hipStream_t s) {
   const size_t lds = (size_t)TN_STAGES * TN_STAGE;
   auto kern = tr_wgrad_group_kernel<T>;
   static bool attr_done = false;
-  if (int rc = tf_set_lds(kern, attr_done)) return rc;
+  if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, s, g);
   VMC_CHECK_LAUNCH();
   return 0;
