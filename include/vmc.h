@@ -244,10 +244,11 @@ int vmc_postnorm_bwd(const void* dy, const void* dy2, const float* sum, const fl
                      uint64_t seed1, float p2, uint64_t seed2, int dtype16, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * K4 — ViT self-attention  softmax(Q K^T / sqrt(dh)) V, no mask, head_dim 64 (MFMA, K/V tile in LDS).
+ * K4 — ViT self-attention  softmax(Q K^T / sqrt(dh)) V, no mask, head_dim 64 (MFMA).
  * Replaces the SDPA inside nn.MultiheadAttention of every CLIP residual block.
  *   qkv 16-bit [F*N, 3*D] packed as the in_proj output: columns [0,D)=Q, [D,2D)=K, [2D,3D)=V, head h at
- *   columns h*64..h*64+63;  out 16-bit [F*N, D].   D = H*64, N <= 288.
+ *   columns h*64..h*64+63;  out 16-bit [F*N, D].   D = H*64, any N >= 1: N <= 288 keeps a head's K/V in LDS,
+ *   longer sequences (ViT-L/14@336px: N = 577) stream 64-key K/V tiles through LDS.
  *   lse f32 [F, H, N] optional (log-sum-exp of the scaled scores, saved for the backward).
  */
 int vmc_attention_vit_fwd(const void* qkv, void* out, float* lse, int F, int N, int H, int dtype16,
@@ -256,7 +257,9 @@ int vmc_attention_vit_fwd(const void* qkv, void* out, float* lse, int F, int N, 
 /* The same attention for the CLASS-TOKEN query only: what the last residual block of the encoder needs (only x[:, 0] reaches
  * ln_post: `x = self.ln_post(x[:, 0, :])`, OpenAI clip model.py; modeling_clip.py:650 pooled_output = last_hidden_state[:, 0]).
  *   q_cls 16-bit [F, D] (the class rows' queries), kv 16-bit [F*N, 2*D] (columns [0,D)=K, [D,2D)=V of every token),
- *   out 16-bit [F, D].  Same kernel, one 16-row query tile per (frame, head) instead of ceil(N/16). */
+ *   out 16-bit [F, D].  Any N >= 1.  N <= 288: same kernel, one 16-row query tile per (frame, head) instead of ceil(N/16);
+ *   longer: one wave per (frame, head) through the key tiles of the streamed kernel.  Either way the class row equals row 0
+ *   of vmc_attention_vit_fwd bit for bit. */
 int vmc_attention_vit_cls_fwd(const void* q_cls, const void* kv, void* out, int F, int N, int H, int dtype16, void* stream);
 
 /* K4/K11/K12 generic masked attention, any head_dim <= 128 with head_dim % 8 == 0.

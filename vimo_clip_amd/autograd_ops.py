@@ -515,7 +515,7 @@ class SelfAttnPackedFn(torch.autograd.Function):
     def forward(ctx, qkv, mask, B, T, H):
         D = qkv.shape[1] // 3
         dh = D // H
-        if mask is None and dh == 64 and T <= 288:
+        if mask is None and dh == 64:           # the ViT kernels: K / V of a head in LDS up to 288 tokens, streamed past that
             out, lse = ops.attention_vit(qkv, B, T, H, want_lse=True)
         else:
             out, lse = ops.attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], mask, B, H, T, T, dh, want_lse=True)

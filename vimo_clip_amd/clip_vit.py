@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .synth import VIT_GEOMETRY
+from .synth import vit_geometry
 
 
 class _LN(nn.Module):
@@ -105,7 +105,8 @@ class VisionTransformer(nn.Module):
 
     @classmethod
     def from_name(cls, name: str, **kw):
-        R, p, D, L, H, E = VIT_GEOMETRY[name]
+        """An OpenAI model name (``ViT-L/14@336px``) or a Hugging Face id (``openai/clip-vit-large-patch14-336``)."""
+        R, p, D, L, H, E = vit_geometry(name)
         return cls(R, p, D, L, H, E, **kw)
 
     def _init_weights(self):

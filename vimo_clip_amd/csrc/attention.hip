@@ -1,5 +1,6 @@
 // Attention kernels (gfx950).
-//   vmc_attention_vit_fwd : CLIP ViT self-attention, head_dim 64, no mask — MFMA, whole K/V head in LDS.
+//   vmc_attention_vit_fwd : CLIP ViT self-attention, head_dim 64, no mask — MFMA, whole K/V head in LDS (N <= 288);
+//                           longer sequences stream K/V through LDS (attention_vit_long.hip).
 //   vmc_attention_fwd/bwd : generic masked attention (TFAM self/cross attention; also the training backward of the ViT
 //                           blocks).  Dispatch, head_dim 64 / 96:
 //                             forward  Tk <= 64                       attn_small_kernel (one wave per (b, h))
@@ -221,6 +222,10 @@ __global__ void __launch_bounds__(64 * NW, NW / 2) attn_vit_kernel(const uint16_
 
 struct VitOperands { const uint16_t *q, *k, *v; size_t ldq, ldkv; int NQ; };
 
+// N > 288 (the whole head no longer fits in LDS): attention_vit_long.hip
+int attn_vit_long_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv, int NQ, void* out, float* lse, int F,
+                      int N, int H, int dtype16, hipStream_t s);
+
 template <typename T, int NT, int NC = 0, int NW = 4, bool REREAD = false, bool PERSIST = false>
 static int launch_vit(const VitOperands& a, void* out, float* lse, int F, int N, int H, hipStream_t stream, int stagger = 0) {
   auto kern = attn_vit_kernel<T, NT, NC, NW, REREAD, PERSIST>;
@@ -254,7 +259,7 @@ static int dispatch_vit(const VitOperands& qkv, void* out, float* lse, int F, in
   if (N <= 128) return launch_vit<T, 8>(qkv, out, lse, F, N, H, s);
   if (N <= 224) return launch_vit<T, 14>(qkv, out, lse, F, N, H, s);
   if (N <= 288) return launch_vit<T, 18>(qkv, out, lse, F, N, H, s);
-  return VMC_E_SHAPE;
+  return attn_vit_long_fwd(qkv.q, qkv.k, qkv.v, qkv.ldq, qkv.ldkv, qkv.NQ, out, lse, F, N, H, T::id, s);   // K / V streamed through LDS
 }
 
 extern "C" int vmc_attention_vit_fwd(const void* qkv, void* out, float* lse, int F, int N, int H, int dtype16, void* stream) {

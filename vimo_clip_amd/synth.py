@@ -75,11 +75,34 @@ VIT_GEOMETRY = {
     "ViT-B/32": (224, 32, 768, 12, 12, 512),
     "ViT-B/16": (224, 16, 768, 12, 12, 512),
     "ViT-L/14": (224, 14, 1024, 24, 16, 768),
+    "ViT-L/14@336px": (336, 14, 1024, 24, 16, 768),
     # tiny geometries for CPU-sized parity tests (dh = 64 like the real ones)
     "ViT-tiny/32": (64, 32, 128, 2, 2, 64),
     "ViT-tiny/16": (64, 16, 128, 2, 2, 64),
     "ViT-tiny/14": (56, 14, 128, 3, 2, 96),
+    "ViT-tiny/14@336px": (336, 14, 128, 2, 2, 96),      # 577 tokens, like ViT-L/14@336px
 }
+
+# Hugging Face ids of the OpenAI towers -> the OpenAI names (the reference's extractor loads the HF id, its student the OpenAI name)
+HF_VIT_NAMES = {
+    "openai/clip-vit-base-patch32": "ViT-B/32",
+    "openai/clip-vit-base-patch16": "ViT-B/16",
+    "openai/clip-vit-large-patch14": "ViT-L/14",
+    "openai/clip-vit-large-patch14-336": "ViT-L/14@336px",
+}
+
+
+def vit_name(name: str) -> str:
+    """The VIT_GEOMETRY key of an OpenAI model name or a Hugging Face id; KeyError (listing the known names) for anything else."""
+    key = HF_VIT_NAMES.get(name, name)
+    if key not in VIT_GEOMETRY:
+        raise KeyError(f"unknown CLIP ViT {name!r}; known names: {', '.join(list(VIT_GEOMETRY) + list(HF_VIT_NAMES))}")
+    return key
+
+
+def vit_geometry(name: str) -> tuple:
+    """(resolution, patch, width, layers, heads, output_dim) of an OpenAI model name or a Hugging Face id."""
+    return VIT_GEOMETRY[vit_name(name)]
 
 
 def vit_state_dict(name: str, seed: int, stress: float = 1.0) -> dict:

@@ -19,6 +19,12 @@ from .dataset import SyntheticSegmentDataset, collate_fn
 from .losses import classification_loss, cross_entropy_loss, distillation_loss
 from .models.student_model import FlowStudentModel
 from .optim import FusedAdam, GradArena
+from .synth import vit_geometry
+
+
+def embed_dim(clip_model_name: str) -> int:
+    """Width of the teacher / student embeddings: the tower's output_dim (KeyError for an unknown name)."""
+    return vit_geometry(clip_model_name)[5]
 
 
 def _batches(ds, batch_size, rank, world):
@@ -54,7 +60,7 @@ def evaluate(model, val_set, device, distillation_loss_mode, class_positive_weig
 def train(args):
     rank, world, local = parallel.init_from_env()
     device = f"cuda:{local}"
-    E = {"ViT-B/32": 512, "ViT-B/16": 512, "ViT-L/14": 768}.get(args.clip_model_name, 512)
+    E = embed_dim(args.clip_model_name)
     single = bool(getattr(args, "single_label", False))
     if getattr(args, "clip_embeddings_dir", None):
         from .dataset import HDF5VideoDataset
