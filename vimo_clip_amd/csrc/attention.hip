@@ -1,14 +1,13 @@
 // Attention kernels (gfx950).
-//   vmc_attention_vit_fwd : CLIP ViT self-attention, head_dim 64, no mask — MFMA, whole K/V head in LDS (N <= 288);
+//   vmc_attention_vit_fwd : CLIP ViT self-attention, head_dim 64, no mask — MFMA, whole K/V head in LDS (attn_vit_kernel);
 //                           longer sequences stream K/V through LDS (attention_vit_long.hip).
 //   vmc_attention_fwd/bwd : generic masked attention (TFAM self/cross attention; also the training backward of the ViT
-//                           blocks).  Dispatch, head_dim 64 / 96:
-//                             forward  Tk <= 64                       attn_small_kernel (one wave per (b, h))
-//                                      Tk > 64                        attention_long.hip (tiled, any length)
-//                             backward Q, K, V, dO of a head in LDS   attn_bwd_mfma_kernel
-//                                      longer                         attention_long.hip (tiled, any length)
-//                           other head dims (<= 128, % 8): the scalar fp32 kernels below, Tq, Tk <= 2048.
+//                           blocks): short-sequence MFMA kernels here, tiled ones in attention_long.hip, scalar fp32 kernels
+//                           for the other head dims.
+// Which kernel a call takes, with which launch, is decided in one place: attn_route.h.  The host code of this file checks and
+// routes each call through it and executes the plan.
 #include "common.h"
+#include "attn_route.h"
 
 // ==================================================================================================
 // ViT forward.  One workgroup = one (frame, head); 4 waves; each wave owns 16-query tiles.
@@ -220,66 +219,52 @@ __global__ void __launch_bounds__(64 * NW, NW / 2) attn_vit_kernel(const uint16_
   }      // (frame, head) walk
 }
 
-struct VitOperands { const uint16_t *q, *k, *v; size_t ldq, ldkv; int NQ; };
-
-// N > 288 (the whole head no longer fits in LDS): attention_vit_long.hip
-int attn_vit_long_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv, int NQ, void* out, float* lse, int F,
-                      int N, int H, int dtype16, hipStream_t s);
-
-template <typename T, int NT, int NC = 0, int NW = 4, bool REREAD = false, bool PERSIST = false>
-static int launch_vit(const VitOperands& a, void* out, float* lse, int F, int N, int H, hipStream_t stream, int stagger = 0) {
-  auto kern = attn_vit_kernel<T, NT, NC, NW, REREAD, PERSIST>;
-  constexpr int LDS = 16 * NT * 128 * 2;
+// ---- host side: attn_vit_route (attn_route.h) picks the kAttnVitInsts entry or the streamed kernels ----
+template <typename T, int I>
+static int launch_vit(const AttnPlan& pl, const AttnVitProblem& p, hipStream_t s) {
+  constexpr AttnVitInst c = kAttnVitInsts[I];
+  auto kern = attn_vit_kernel<T, c.nt, c.nc, c.nw, c.reread, c.persist>;
   static bool lds_set = false;
-  if (int rc = set_max_lds(lds_set, LDS, kern)) return rc;
-  const int grid = PERSIST ? (F * H < 512 ? F * H : 512) : F * H;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), LDS, stream, a.q, a.k, a.v, (uint16_t*)out, lse, N, a.NQ, H, a.ldq, a.ldkv, 0.125f, F * H,
-                     stagger);
+  if (int rc = set_max_lds(lds_set, pl.lds, kern)) return rc;
+  hipLaunchKernelGGL(kern, dim3(pl.grid[0]), dim3(pl.block), pl.lds, s, (const uint16_t*)p.q, (const uint16_t*)p.k, (const uint16_t*)p.v,
+                     (uint16_t*)p.out, p.lse, p.N, p.NQ, p.H, p.ldq, p.ldkv, 0.125f, p.F * p.H, pl.stagger);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T>
-static int dispatch_vit(const VitOperands& qkv, void* out, float* lse, int F, int N, int H, hipStream_t s) {
-  if (N == 257 && qkv.NQ == N) {                                             // ViT-L/14 @ 224
-    // default: 8 waves, K fragments re-read per tile (112 VGPRs, 4 waves per SIMD): 167-169 us against 171-174 us per ViT-L/14 layer.
-    // VMC_ATTN_VARIANT (builder A/B switch): 9 = the 4-wave kernel of round 2 (252 VGPRs), 2 = 4 waves + re-read, 10+s / 20+s =
-    // persistent walks with a stagger of s sleeps (measured slower or equal: profiles/README.md)
-    static const int variant = getenv("VMC_ATTN_VARIANT") ? atoi(getenv("VMC_ATTN_VARIANT")) : 1;
-    if (variant == 1) return launch_vit<T, 18, 257, 8, true>(qkv, out, lse, F, N, H, s);
-    if (variant == 2) return launch_vit<T, 18, 257, 4, true>(qkv, out, lse, F, N, H, s);
-    if (variant >= 10 && variant < 20) return launch_vit<T, 18, 257, 4, false, true>(qkv, out, lse, F, N, H, s, variant - 10);
-    if (variant >= 20 && variant < 30) return launch_vit<T, 18, 257, 8, true, true>(qkv, out, lse, F, N, H, s, variant - 20);
+static int vit_exec(const AttnPlan& pl, const AttnVitProblem& p, hipStream_t s) {
+  static_assert(kAttnVitInstCount == 12, "one case per entry of kAttnVitInsts");
+  switch (pl.vit) {
+    case 0: return launch_vit<T, 0>(pl, p, s); case 1: return launch_vit<T, 1>(pl, p, s); case 2: return launch_vit<T, 2>(pl, p, s);
+    case 3: return launch_vit<T, 3>(pl, p, s); case 4: return launch_vit<T, 4>(pl, p, s); case 5: return launch_vit<T, 5>(pl, p, s);
+    case 6: return launch_vit<T, 6>(pl, p, s); case 7: return launch_vit<T, 7>(pl, p, s); case 8: return launch_vit<T, 8>(pl, p, s);
+    case 9: return launch_vit<T, 9>(pl, p, s); case 10: return launch_vit<T, 10>(pl, p, s); case 11: return launch_vit<T, 11>(pl, p, s);
   }
-  if (N == 257) return launch_vit<T, 18, 257>(qkv, out, lse, F, N, H, s);   // ViT-L/14 @ 224
-  if (N == 197) return launch_vit<T, 14, 197>(qkv, out, lse, F, N, H, s);   // ViT-B/16
-  if (N == 50) return launch_vit<T, 4, 50>(qkv, out, lse, F, N, H, s);      // ViT-B/32
-  if (N <= 32) return launch_vit<T, 2>(qkv, out, lse, F, N, H, s);
-  if (N <= 64) return launch_vit<T, 4>(qkv, out, lse, F, N, H, s);
-  if (N <= 128) return launch_vit<T, 8>(qkv, out, lse, F, N, H, s);
-  if (N <= 224) return launch_vit<T, 14>(qkv, out, lse, F, N, H, s);
-  if (N <= 288) return launch_vit<T, 18>(qkv, out, lse, F, N, H, s);
-  return attn_vit_long_fwd(qkv.q, qkv.k, qkv.v, qkv.ldq, qkv.ldkv, qkv.NQ, out, lse, F, N, H, T::id, s);   // K / V streamed through LDS
+  return VMC_E_ARG;
+}
+
+static const AttnOverrides& attn_overrides() {
+  static const AttnOverrides o = attn_overrides_from_env();
+  return o;
+}
+
+static int vit_impl(const AttnVitProblem& p, void* stream) {
+  const AttnPlan pl = attn_vit_route(p, attn_overrides());
+  if (pl.rc) return pl.rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (pl.kernel != ATTN_VIT) return attn_vit_long_fwd(pl, p, s);      // K / V streamed through LDS
+  return p.dtype16 == VMC_BF16 ? vit_exec<BF16>(pl, p, s) : vit_exec<F16>(pl, p, s);
 }
 
 extern "C" int vmc_attention_vit_fwd(const void* qkv, void* out, float* lse, int F, int N, int H, int dtype16, void* stream) {
-  if (!qkv || !out || F <= 0 || N <= 0 || H <= 0) return VMC_E_ARG;
-  if (((uintptr_t)qkv | (uintptr_t)out) & 15) return VMC_E_ALIGN;
   const size_t D = (size_t)H * 64;
-  const VitOperands a = {(const uint16_t*)qkv, (const uint16_t*)qkv + D, (const uint16_t*)qkv + 2 * D, 3 * D, 3 * D, N};
-  if (dtype16 == VMC_BF16) return dispatch_vit<BF16>(a, out, lse, F, N, H, (hipStream_t)stream);
-  if (dtype16 == VMC_F16) return dispatch_vit<F16>(a, out, lse, F, N, H, (hipStream_t)stream);
-  return VMC_E_DTYPE;
+  return vit_impl({qkv, (const uint16_t*)qkv + D, (const uint16_t*)qkv + 2 * D, out, lse, 3 * D, 3 * D, F, N, N, H, dtype16}, stream);
 }
 
 extern "C" int vmc_attention_vit_cls_fwd(const void* q_cls, const void* kv, void* out, int F, int N, int H, int dtype16, void* stream) {
-  if (!q_cls || !kv || !out || F <= 0 || N <= 0 || H <= 0) return VMC_E_ARG;
-  if (((uintptr_t)q_cls | (uintptr_t)kv | (uintptr_t)out) & 15) return VMC_E_ALIGN;
   const size_t D = (size_t)H * 64;
-  const VitOperands a = {(const uint16_t*)q_cls, (const uint16_t*)kv, (const uint16_t*)kv + D, D, 2 * D, 1};
-  if (dtype16 == VMC_BF16) return dispatch_vit<BF16>(a, out, nullptr, F, N, H, (hipStream_t)stream);
-  if (dtype16 == VMC_F16) return dispatch_vit<F16>(a, out, nullptr, F, N, H, (hipStream_t)stream);
-  return VMC_E_DTYPE;
+  return vit_impl({q_cls, kv, (const uint16_t*)kv + D, out, nullptr, D, 2 * D, F, N, 1, H, dtype16}, stream);
 }
 
 // ==================================================================================================
@@ -423,27 +408,9 @@ __global__ void __launch_bounds__(64) attn_small_kernel(const uint16_t* __restri
   }
 }
 
-template <typename T>
-static int launch_small(const void* q, const void* k, const void* v, const uint8_t* mask, void* out, float* lse, int B, int H, int Tq,
-                        int Tk, int dh, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, uint64_t seed, hipStream_t s) {
-#define VMC_SMALL(DHV, NTV)                                                                                                      \
-  hipLaunchKernelGGL((attn_small_kernel<T, DHV, NTV>), dim3(B * H), dim3(64), 0, s, (const uint16_t*)q, (const uint16_t*)k,      \
-                     (const uint16_t*)v, mask, (uint16_t*)out, lse, H, Tq, Tk, ldq, ldk, ldv, ldo, scale, drop_p, seed)
-  if (dh == 64 && Tk <= 32) VMC_SMALL(64, 2);
-  else if (dh == 64) VMC_SMALL(64, 4);
-  else if (dh == 96 && Tk <= 32) VMC_SMALL(96, 2);
-  else VMC_SMALL(96, 4);
-#undef VMC_SMALL
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
 // ==================================================================================================
-// Generic masked attention, fp32 math.  One wave per (batch, head, query).  Scores live in LDS.
+// Generic masked attention, fp32 math.  One wave per (batch, head, query).  Scores live in LDS (ATT_MAX_TK: attn_route.h).
 // ==================================================================================================
-#define ATT_MAX_TK 2048
-#define ATT_MAX_DH 128
-
 template <typename T>
 __device__ inline float dot16(const uint16_t* __restrict__ a16, const float* __restrict__ bf, int dh) {
   float acc = 0.f;
@@ -871,133 +838,85 @@ __global__ void __launch_bounds__(256, 3) attn_bwd_mfma_kernel(const uint16_t* _
   }  // tasks
 }
 
-template <typename T, int DH>
-static int launch_bwd_mfma(const void* q, const void* k, const void* v, const uint8_t* mask, const void* out, const void* dout,
-                           const float* lse, void* dq, void* dk, void* dv, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv,
-                           int ldo, int lddq, int lddk, int lddv, float scale, float drop_p, uint64_t seed, hipStream_t s) {
-  const int TQP = (Tq + 31) & ~31, TKP = (Tk + 31) & ~31;
-  int RS = DH * 2 + 16;
-  size_t lds = (size_t)2 * (TQP + TKP) * RS + (size_t)2 * TQP * sizeof(float);
-  if (lds > 160 * 1024) {
-    RS = DH * 2;
-    lds = (size_t)2 * (TQP + TKP) * RS + (size_t)2 * TQP * sizeof(float);
-  }
-  if (lds > 160 * 1024) return VMC_E_SHAPE;
-  auto kern = attn_bwd_mfma_kernel<T, DH>;
-  static size_t attr = 0;
-  if (lds > attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr = 160 * 1024;
-  }
-  // one wave per tile task, at most four: a 16-token clip (one key tile + one query tile) runs as a 2-wave workgroup, which lets
-  // five of them share a CU instead of three 4-wave ones with two idle waves each
-  const int tasks = (Tk + 15) / 16 + (Tq + 15) / 16;
-  const int threads = 64 * (tasks < 4 ? tasks : 4);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(threads), lds, s, (const uint16_t*)q, (const uint16_t*)k, (const uint16_t*)v, mask,
-                     (const uint16_t*)out, (const uint16_t*)dout, lse, (uint16_t*)dq, (uint16_t*)dk, (uint16_t*)dv, H, Tq, Tk, ldq, ldk,
-                     ldv, ldo, lddq, lddk, lddv, scale, RS, drop_p, seed);
+// ==================================================================================================
+// Host side of the masked attention: attn_fwd_route / attn_bwd_route (attn_route.h) check a call and pick its kernels; the
+// tiled ones are executed by attention_long.hip, the others below.
+// ==================================================================================================
+template <typename T, int DH, int NT>
+static int launch_small(const AttnPlan& pl, const AttnFwdProblem& p, float scale, hipStream_t s) {
+  hipLaunchKernelGGL((attn_small_kernel<T, DH, NT>), dim3(pl.grid[0]), dim3(pl.block), 0, s, (const uint16_t*)p.q, (const uint16_t*)p.k,
+                     (const uint16_t*)p.v, p.mask, (uint16_t*)p.out, p.lse, p.H, p.Tq, p.Tk, p.ldq, p.ldk, p.ldv, p.ldo, scale, p.dropout_p,
+                     p.seed);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
-static int check_generic(int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo) {
-  if (B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return VMC_E_ARG;
-  if (dh <= 0 || dh > ATT_MAX_DH || (dh % 8)) return VMC_E_SHAPE;
-  if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8)) return VMC_E_ALIGN;
+template <typename T>
+static int fwd_exec(const AttnPlan& pl, const AttnFwdProblem& p, hipStream_t s) {
+  const float scale = 1.0f / sqrtf((float)p.dh);
+  if (pl.kernel == ATTN_SMALL) {
+    if (pl.dh == 64) return pl.nt == 2 ? launch_small<T, 64, 2>(pl, p, scale, s) : launch_small<T, 64, 4>(pl, p, scale, s);
+    return pl.nt == 2 ? launch_small<T, 96, 2>(pl, p, scale, s) : launch_small<T, 96, 4>(pl, p, scale, s);
+  }
+  hipLaunchKernelGGL(attn_generic_fwd<T>, dim3(pl.grid[0]), dim3(pl.block), 0, s, (const uint16_t*)p.q, (const uint16_t*)p.k,
+                     (const uint16_t*)p.v, p.mask, (uint16_t*)p.out, p.lse, p.H, p.Tq, p.Tk, p.dh, p.ldq, p.ldk, p.ldv, p.ldo, scale,
+                     p.dropout_p, (unsigned long long)p.seed);
+  VMC_CHECK_LAUNCH();
   return 0;
 }
-// the scalar kernels keep a score row in LDS: ATT_MAX_TK floats
-static int check_scalar_len(int Tq, int Tk) { return (Tk > ATT_MAX_TK || Tq > ATT_MAX_TK) ? VMC_E_SHAPE : 0; }
-
-// Tiled kernels of attention_long.hip.  Beyond check_generic they store 16-bit results as 8-byte words (output bases 8-byte
-// aligned, output strides % 4) and the backward reads O as 16-byte words; a caller that does not give that alignment keeps
-// the scalar kernels.
-int attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out, float* lse, int B, int H, int Tq, int Tk,
-                  int dh, int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, uint64_t seed, int dtype16, hipStream_t s);
-int attn_long_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* out, const void* dout, const float* lse,
-                  void* dq, void* dk, void* dv, float* delta, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo,
-                  int lddq, int lddk, int lddv, float scale, float drop_p, uint64_t seed, int dtype16, hipStream_t s);
 
 extern "C" int vmc_attention_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, void* out,
                                  float* lse, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo,
                                  float dropout_p, uint64_t dropout_seed, int dtype16, void* stream) {
-  if (!q || !k || !v || !out || dropout_p < 0.f || dropout_p >= 1.f) return VMC_E_ARG;
-  int rc = check_generic(B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo);
-  if (rc) return rc;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) return VMC_E_ALIGN;
-  const float scale = 1.0f / sqrtf((float)dh);
-  if (Tk <= 64 && (dh == 64 || dh == 96) && (ldo % 4) == 0) {   // short sequences: MFMA kernel, one wave per (b, h)
-    if (dtype16 == VMC_BF16) return launch_small<BF16>(q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p, dropout_seed, (hipStream_t)stream);
-    if (dtype16 == VMC_F16) return launch_small<F16>(q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p, dropout_seed, (hipStream_t)stream);
-    return VMC_E_DTYPE;
-  }
-  if ((dh == 64 || dh == 96) && (ldo % 4) == 0 && ((uintptr_t)out & 7) == 0)   // longer sequences: tiled MFMA kernel
-    return attn_long_fwd(q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p, dropout_seed, dtype16,
-                         (hipStream_t)stream);
-  if ((rc = check_scalar_len(Tq, Tk))) return rc;
-  dim3 grid(B * H * Tq);
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(attn_generic_fwd<BF16>, grid, dim3(64), 0, (hipStream_t)stream, (const uint16_t*)q, (const uint16_t*)k,
-                       (const uint16_t*)v, key_mask, (uint16_t*)out, lse, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p,
-                       (unsigned long long)dropout_seed);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(attn_generic_fwd<F16>, grid, dim3(64), 0, (hipStream_t)stream, (const uint16_t*)q, (const uint16_t*)k,
-                       (const uint16_t*)v, key_mask, (uint16_t*)out, lse, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, scale, dropout_p,
-                       (unsigned long long)dropout_seed);
-  else
-    return VMC_E_DTYPE;
+  const AttnFwdProblem p = {q, k, v, key_mask, out, lse, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, dropout_p, dropout_seed, dtype16};
+  const AttnPlan pl = attn_fwd_route(p);
+  if (pl.rc) return pl.rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (pl.kernel == ATTN_LONG_FWD) return attn_long_fwd(pl, p, s);
+  return dtype16 == VMC_BF16 ? fwd_exec<BF16>(pl, p, s) : fwd_exec<F16>(pl, p, s);
+}
+
+template <typename T, int DH>
+static int launch_bwd_mfma(const AttnPlan& pl, const AttnBwdProblem& p, float scale, hipStream_t s) {
+  auto kern = attn_bwd_mfma_kernel<T, DH>;
+  static bool lds_set = false;
+  if (int rc = set_max_lds(lds_set, ATT_BWD_MAX_LDS, kern)) return rc;
+  hipLaunchKernelGGL(kern, dim3(pl.grid[0]), dim3(pl.block), pl.lds, s, (const uint16_t*)p.q, (const uint16_t*)p.k, (const uint16_t*)p.v,
+                     p.mask, (const uint16_t*)p.out, (const uint16_t*)p.dout, p.lse, (uint16_t*)p.dq, (uint16_t*)p.dk, (uint16_t*)p.dv, p.H,
+                     p.Tq, p.Tk, p.ldq, p.ldk, p.ldv, p.ldo, p.lddq, p.lddk, p.lddv, scale, pl.rs, p.dropout_p, p.seed);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" size_t vmc_attention_bwd_workspace_bytes(int B, int H, int Tq) { return (size_t)B * H * Tq * sizeof(float); }
+template <typename T>
+static int bwd_exec(const AttnPlan& pl, const AttnBwdProblem& p, hipStream_t s) {
+  const float scale = 1.0f / sqrtf((float)p.dh);
+  if (pl.kernel == ATTN_BWD_MFMA)
+    return pl.dh == 64 ? launch_bwd_mfma<T, 64>(pl, p, scale, s) : launch_bwd_mfma<T, 96>(pl, p, scale, s);
+  const uint16_t *q = (const uint16_t*)p.q, *k = (const uint16_t*)p.k, *v = (const uint16_t*)p.v, *dout = (const uint16_t*)p.dout;
+  float* delta = (float*)p.workspace;
+  hipLaunchKernelGGL(attn_generic_bwd_q<T>, dim3(pl.grid[0]), dim3(pl.block), 0, s, q, k, v, p.mask, (const uint16_t*)p.out, dout, p.lse,
+                     (uint16_t*)p.dq, delta, p.H, p.Tq, p.Tk, p.dh, p.ldq, p.ldk, p.ldv, p.ldo, p.lddq, scale, p.dropout_p,
+                     (unsigned long long)p.seed);
+  hipLaunchKernelGGL(attn_generic_bwd_kv<T>, dim3(pl.grid[1]), dim3(pl.block), 0, s, q, k, v, p.mask, dout, p.lse, delta, (uint16_t*)p.dk,
+                     (uint16_t*)p.dv, p.H, p.Tq, p.Tk, p.dh, p.ldq, p.ldk, p.ldv, p.ldo, p.lddk, p.lddv, scale, p.dropout_p,
+                     (unsigned long long)p.seed);
+  VMC_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t vmc_attention_bwd_workspace_bytes(int B, int H, int Tq) { return attn_bwd_workspace_bytes(B, H, Tq); }
 
 extern "C" int vmc_attention_bwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, const void* out,
                                  const void* dout, const float* lse, void* dq, void* dk, void* dv, int B, int H, int Tq,
                                  int Tk, int dh, int ldq, int ldk, int ldv, int ldo, int lddq, int lddk, int lddv,
                                  float dropout_p, uint64_t dropout_seed, void* workspace, size_t workspace_bytes, int dtype16,
                                  void* stream) {
-  if (!q || !k || !v || !out || !dout || !lse || !dq || !dk || !dv || !workspace) return VMC_E_ARG;
-  int rc = check_generic(B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo);
-  if (rc) return rc;
-  if (workspace_bytes < vmc_attention_bwd_workspace_bytes(B, H, Tq)) return VMC_E_ARG;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)dout) & 15) return VMC_E_ALIGN;
-  const float scale = 1.0f / sqrtf((float)dh);
-  if ((dh == 64 || dh == 96) && ((lddq | lddk | lddv | ldo) % 4) == 0) {   // MFMA path when the head fits in LDS
-    const int TQP = (Tq + 31) & ~31, TKP = (Tk + 31) & ~31;
-    if ((size_t)2 * (TQP + TKP) * dh * 2 + (size_t)2 * TQP * sizeof(float) <= 160 * 1024) {
-      hipStream_t st = (hipStream_t)stream;
-      if (dtype16 == VMC_BF16)
-        return dh == 64 ? launch_bwd_mfma<BF16, 64>(q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, dropout_p, dropout_seed, st)
-                        : launch_bwd_mfma<BF16, 96>(q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, dropout_p, dropout_seed, st);
-      if (dtype16 == VMC_F16)
-        return dh == 64 ? launch_bwd_mfma<F16, 64>(q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, dropout_p, dropout_seed, st)
-                        : launch_bwd_mfma<F16, 96>(q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, dropout_p, dropout_seed, st);
-      return VMC_E_DTYPE;
-    }
-    if ((((uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) & 7) == 0 && ((uintptr_t)out & 15) == 0)   // tiled MFMA kernels
-      return attn_long_bwd(q, k, v, key_mask, out, dout, lse, dq, dk, dv, (float*)workspace, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, lddq,
-                           lddk, lddv, scale, dropout_p, dropout_seed, dtype16, (hipStream_t)stream);
-  }
-  if ((rc = check_scalar_len(Tq, Tk))) return rc;
-  float* delta = (float*)workspace;
-  hipStream_t s = (hipStream_t)stream;
-#define VMC_LAUNCH_BWD(TT)                                                                                                   \
-  hipLaunchKernelGGL(attn_generic_bwd_q<TT>, dim3(B * H * Tq), dim3(64), 0, s, (const uint16_t*)q, (const uint16_t*)k,       \
-                     (const uint16_t*)v, key_mask, (const uint16_t*)out, (const uint16_t*)dout, lse, (uint16_t*)dq, delta, H, \
-                     Tq, Tk, dh, ldq, ldk, ldv, ldo, lddq, scale, dropout_p, (unsigned long long)dropout_seed);                                                            \
-  hipLaunchKernelGGL(attn_generic_bwd_kv<TT>, dim3(B * H * Tk), dim3(64), 0, s, (const uint16_t*)q, (const uint16_t*)k,      \
-                     (const uint16_t*)v, key_mask, (const uint16_t*)dout, lse, delta, (uint16_t*)dk, (uint16_t*)dv, H, Tq, Tk, \
-                     dh, ldq, ldk, ldv, ldo, lddk, lddv, scale, dropout_p, (unsigned long long)dropout_seed);
-  if (dtype16 == VMC_BF16) {
-    VMC_LAUNCH_BWD(BF16)
-  } else if (dtype16 == VMC_F16) {
-    VMC_LAUNCH_BWD(F16)
-  } else {
-    return VMC_E_DTYPE;
-  }
-#undef VMC_LAUNCH_BWD
-  VMC_CHECK_LAUNCH();
-  return 0;
+  const AttnBwdProblem p = {q, k, v, key_mask, out, dout, lse, dq, dk, dv, B, H, Tq, Tk, dh, ldq, ldk, ldv, ldo, lddq, lddk, lddv,
+                            dropout_p, dropout_seed, workspace, workspace_bytes, dtype16};
+  const AttnPlan pl = attn_bwd_route(p);
+  if (pl.rc) return pl.rc;
+  const hipStream_t s = (hipStream_t)stream;
+  if (pl.kernel == ATTN_LONG_BWD) return attn_long_bwd(pl, p, s);
+  return dtype16 == VMC_BF16 ? bwd_exec<BF16>(pl, p, s) : bwd_exec<F16>(pl, p, s);
 }

@@ -1,6 +1,6 @@
 // Tiled ("flash") masked attention on MFMA for sequences of any length (gfx950): head_dim 64 / 96, bf16 / f16.
 // vmc_attention_fwd / vmc_attention_bwd (attention.hip) dispatch here every shape their short-sequence kernels do not take:
-// the forward beyond 64 keys, the backward once Q, K, V and dO of a head no longer fit in LDS.
+// the forward beyond 64 keys, the backward once Q, K, V and dO of a head no longer fit in LDS (conditions: attn_route.h).
 //
 //   forward : one workgroup = 4 waves = one (batch, head, block of 64 query rows); a wave owns 16 query rows.  K / V tiles of
 //             64 keys stream through two LDS buffers (the next tile's global loads are issued before this tile's MFMAs and
@@ -18,11 +18,12 @@
 // yields NaN in out and lse, written as a constant: this file is built like attention.hip with -fno-honor-nans, where NaN
 // arithmetic may be folded away.
 #include "common.h"
+#include "attn_route.h"
 
 namespace {
 
-constexpr int LT = 64;          // rows of every tile (queries per workgroup, keys per K / V tile)
-constexpr int NTH = 256;        // 4 waves
+constexpr int LT = ATT_LONG_LT;      // rows of every tile (queries per workgroup, keys per K / V tile)
+constexpr int NTH = ATT_LONG_NTH;    // 4 waves
 constexpr float LOG2E = 1.4426950408889634f;
 
 template <typename T>
@@ -467,59 +468,39 @@ __global__ void __launch_bounds__(NTH) attn_long_bwd_q_kernel(const uint16_t* __
 }
 
 template <typename T, int DH>
-int launch_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out, float* lse, int B, int H, int Tq, int Tk,
-               int ldq, int ldk, int ldv, int ldo, float scale, float drop_p, uint64_t seed, hipStream_t s) {
-  const size_t grid = (size_t)B * H * ((Tq + LT - 1) / LT);
-  if (grid > 0x7FFFFFFF) return VMC_E_SHAPE;
-  hipLaunchKernelGGL((attn_long_fwd_kernel<T, DH>), dim3((unsigned)grid), dim3(NTH), 0, s, (const uint16_t*)q, (const uint16_t*)k,
-                     (const uint16_t*)v, mask, (uint16_t*)out, lse, H, Tq, Tk, ldq, ldk, ldv, ldo, scale, drop_p, seed);
+int launch_fwd(const AttnPlan& pl, const AttnFwdProblem& p, hipStream_t s) {
+  hipLaunchKernelGGL((attn_long_fwd_kernel<T, DH>), dim3(pl.grid[0]), dim3(pl.block), 0, s, (const uint16_t*)p.q, (const uint16_t*)p.k,
+                     (const uint16_t*)p.v, p.mask, (uint16_t*)p.out, p.lse, p.H, p.Tq, p.Tk, p.ldq, p.ldk, p.ldv, p.ldo,
+                     1.0f / sqrtf((float)p.dh), p.dropout_p, p.seed);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int DH>
-int launch_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* out, const void* dout, const float* lse,
-               void* dq, void* dk, void* dv, float* delta, int B, int H, int Tq, int Tk, int ldq, int ldk, int ldv, int ldo, int lddq,
-               int lddk, int lddv, float scale, float drop_p, uint64_t seed, hipStream_t s) {
-  const size_t items = (size_t)B * H * Tq;
-  const size_t gkv = (size_t)B * H * ((Tk + LT - 1) / LT), gq = (size_t)B * H * ((Tq + LT - 1) / LT), gd = (items * 4 + 255) / 256;
-  if (gkv > 0x7FFFFFFF || gq > 0x7FFFFFFF || gd > 0x7FFFFFFF) return VMC_E_SHAPE;
-  hipLaunchKernelGGL((attn_long_delta_kernel<T, DH>), dim3((unsigned)gd), dim3(256), 0, s, (const uint16_t*)out, (const uint16_t*)dout, delta,
-                     H, Tq, ldo, items);
-  hipLaunchKernelGGL((attn_long_bwd_kv_kernel<T, DH>), dim3((unsigned)gkv), dim3(NTH), 0, s, (const uint16_t*)q, (const uint16_t*)k,
-                     (const uint16_t*)v, mask, (const uint16_t*)dout, lse, delta, (uint16_t*)dk, (uint16_t*)dv, H, Tq, Tk, ldq, ldk, ldv,
-                     ldo, lddk, lddv, scale, drop_p, seed);
-  hipLaunchKernelGGL((attn_long_bwd_q_kernel<T, DH>), dim3((unsigned)gq), dim3(NTH), 0, s, (const uint16_t*)q, (const uint16_t*)k,
-                     (const uint16_t*)v, mask, (const uint16_t*)dout, lse, delta, (uint16_t*)dq, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq,
-                     scale, drop_p, seed);
+int launch_bwd(const AttnPlan& pl, const AttnBwdProblem& p, hipStream_t s) {
+  const uint16_t *q = (const uint16_t*)p.q, *k = (const uint16_t*)p.k, *v = (const uint16_t*)p.v, *dout = (const uint16_t*)p.dout;
+  const float scale = 1.0f / sqrtf((float)p.dh);
+  float* delta = (float*)p.workspace;
+  hipLaunchKernelGGL((attn_long_delta_kernel<T, DH>), dim3(pl.grid[0]), dim3(pl.block), 0, s, (const uint16_t*)p.out, dout, delta, p.H,
+                     p.Tq, p.ldo, (size_t)p.B * p.H * p.Tq);
+  hipLaunchKernelGGL((attn_long_bwd_kv_kernel<T, DH>), dim3(pl.grid[1]), dim3(pl.block), 0, s, q, k, v, p.mask, dout, p.lse, delta,
+                     (uint16_t*)p.dk, (uint16_t*)p.dv, p.H, p.Tq, p.Tk, p.ldq, p.ldk, p.ldv, p.ldo, p.lddk, p.lddv, scale, p.dropout_p,
+                     p.seed);
+  hipLaunchKernelGGL((attn_long_bwd_q_kernel<T, DH>), dim3(pl.grid[2]), dim3(pl.block), 0, s, q, k, v, p.mask, dout, p.lse, delta,
+                     (uint16_t*)p.dq, p.H, p.Tq, p.Tk, p.ldq, p.ldk, p.ldv, p.ldo, p.lddq, scale, p.dropout_p, p.seed);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 }  // namespace
 
-// Entry points for attention.hip's dispatch (not part of the C ABI).  dh is 64 or 96; the caller has checked the alignment
-// (attn_long_aligned in attention.hip).
-__attribute__((visibility("hidden"))) int attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* mask, void* out,
-                                                        float* lse, int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv,
-                                                        int ldo, float scale, float drop_p, uint64_t seed, int dtype16, hipStream_t s) {
-#define VMC_LONG_FWD(TT, DHV) return launch_fwd<TT, DHV>(q, k, v, mask, out, lse, B, H, Tq, Tk, ldq, ldk, ldv, ldo, scale, drop_p, seed, s)
-  if (dtype16 == VMC_BF16) { if (dh == 64) VMC_LONG_FWD(BF16, 64); else VMC_LONG_FWD(BF16, 96); }
-  if (dtype16 == VMC_F16) { if (dh == 64) VMC_LONG_FWD(F16, 64); else VMC_LONG_FWD(F16, 96); }
-#undef VMC_LONG_FWD
-  return VMC_E_DTYPE;
+// The executors of attn_route.h's ATTN_LONG_FWD / ATTN_LONG_BWD plans (declared in common.h).
+int attn_long_fwd(const AttnPlan& pl, const AttnFwdProblem& p, hipStream_t s) {
+  if (p.dtype16 == VMC_BF16) return pl.dh == 64 ? launch_fwd<BF16, 64>(pl, p, s) : launch_fwd<BF16, 96>(pl, p, s);
+  return pl.dh == 64 ? launch_fwd<F16, 64>(pl, p, s) : launch_fwd<F16, 96>(pl, p, s);
 }
 
-__attribute__((visibility("hidden"))) int attn_long_bwd(const void* q, const void* k, const void* v, const uint8_t* mask, const void* out,
-                                                        const void* dout, const float* lse, void* dq, void* dk, void* dv, float* delta,
-                                                        int B, int H, int Tq, int Tk, int dh, int ldq, int ldk, int ldv, int ldo, int lddq,
-                                                        int lddk, int lddv, float scale, float drop_p, uint64_t seed, int dtype16,
-                                                        hipStream_t s) {
-#define VMC_LONG_BWD(TT, DHV)                                                                                                           \
-  return launch_bwd<TT, DHV>(q, k, v, mask, out, dout, lse, dq, dk, dv, delta, B, H, Tq, Tk, ldq, ldk, ldv, ldo, lddq, lddk, lddv, scale, \
-                             drop_p, seed, s)
-  if (dtype16 == VMC_BF16) { if (dh == 64) VMC_LONG_BWD(BF16, 64); else VMC_LONG_BWD(BF16, 96); }
-  if (dtype16 == VMC_F16) { if (dh == 64) VMC_LONG_BWD(F16, 64); else VMC_LONG_BWD(F16, 96); }
-#undef VMC_LONG_BWD
-  return VMC_E_DTYPE;
+int attn_long_bwd(const AttnPlan& pl, const AttnBwdProblem& p, hipStream_t s) {
+  if (p.dtype16 == VMC_BF16) return pl.dh == 64 ? launch_bwd<BF16, 64>(pl, p, s) : launch_bwd<BF16, 96>(pl, p, s);
+  return pl.dh == 64 ? launch_bwd<F16, 64>(pl, p, s) : launch_bwd<F16, 96>(pl, p, s);
 }

@@ -1,5 +1,5 @@
 // CLIP ViT self-attention past the in-LDS kernel's 288 tokens (gfx950): head_dim 64, no mask, bf16 / f16.
-// vmc_attention_vit_fwd / vmc_attention_vit_cls_fwd (attention.hip) dispatch here for N > 288 (ViT-L/14@336px: N = 577).
+// vmc_attention_vit_fwd / vmc_attention_vit_cls_fwd (attention.hip, attn_route.h) dispatch here for N > 288 (ViT-L/14@336px: N = 577).
 //
 //   full    : one workgroup = 4 waves = one (frame, head, block of 128 query rows); a wave owns two 16-row query tiles whose Q
 //             fragments stay in registers.  K / V move in 64-key tiles through two LDS buffers, staged through registers: the next
@@ -16,14 +16,16 @@
 // Any other N > 288 takes the runtime-N instance (no upper limit).  Keys past N are staged as zero rows, so no stale LDS reaches an MFMA.
 // Built with -fno-honor-nans like attention.hip: scores are finite or -inf.
 #include "common.h"
+#include "attn_route.h"
 
 namespace {
 
-constexpr int KT = 64;                        // keys per K / V tile
+constexpr int KT = ATT_VL_KT;                 // keys per K / V tile
 constexpr int TILE_BYTES = KT * 128;          // one 64-key x 64-column 16-bit image
 constexpr int BUF_BYTES = 2 * TILE_BYTES;     // K | V
-constexpr int NW = 4;                         // waves per workgroup (both kernels)
-constexpr int QROWS = NW * 32;                // query rows per workgroup of the full kernel
+constexpr int NW = ATT_VL_NW;                 // waves per workgroup (both kernels)
+constexpr int QROWS = ATT_VL_QROWS;           // query rows per workgroup of the full kernel
+static_assert(NW * 2 * BUF_BYTES == ATT_VL_CLS_LDS, "the class-query kernel's per-wave K / V buffers");
 constexpr float LOG2E = 1.4426950408889634f;
 
 __device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -259,50 +261,26 @@ __global__ void __launch_bounds__(64 * NW) attn_vit_long_cls_kernel(const uint16
 }
 
 template <typename T, int NC>
-int launch_full(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv, void* out, float* lse, int F, int N, int H,
-                hipStream_t s) {
-  const size_t grid = (size_t)F * H * ((N + QROWS - 1) / QROWS);
-  if (grid > 0x7FFFFFFF) return VMC_E_SHAPE;
-  hipLaunchKernelGGL((attn_vit_long_kernel<T, NC>), dim3((unsigned)grid), dim3(64 * NW), 0, s, q, k, v, (uint16_t*)out, lse, N, H, ldq, ldkv,
-                     0.125f);
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T, int NC>
-int launch_cls(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv, void* out, int F, int N, int H,
-               hipStream_t s) {
-  auto kern = attn_vit_long_cls_kernel<T, NC>;
-  constexpr int LDS = NW * 2 * BUF_BYTES;                                // 128 KB
-  static bool lds_set = false;
-  if (int rc = set_max_lds(lds_set, LDS, kern)) return rc;
-  const size_t n_bh = (size_t)F * H;
-  if (n_bh > 0x7FFFFFFF) return VMC_E_SHAPE;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((n_bh + NW - 1) / NW)), dim3(64 * NW), LDS, s, q, k, v, (uint16_t*)out, N, H, (int)n_bh, ldq, ldkv,
-                     0.125f);
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
-template <typename T>
-int dispatch(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv, int NQ, void* out, float* lse, int F, int N,
-             int H, hipStream_t s) {
-  if (NQ == 1) {
-    if (N == 577) return launch_cls<T, 577>(q, k, v, ldq, ldkv, out, F, N, H, s);      // ViT-L/14@336px
-    return launch_cls<T, 0>(q, k, v, ldq, ldkv, out, F, N, H, s);
+int launch(const AttnPlan& pl, const AttnVitProblem& p, hipStream_t s) {
+  const uint16_t *q = (const uint16_t*)p.q, *k = (const uint16_t*)p.k, *v = (const uint16_t*)p.v;
+  if (pl.kernel == ATTN_VIT_LONG_CLS) {
+    auto kern = attn_vit_long_cls_kernel<T, NC>;
+    static bool lds_set = false;
+    if (int rc = set_max_lds(lds_set, pl.lds, kern)) return rc;
+    hipLaunchKernelGGL(kern, dim3(pl.grid[0]), dim3(pl.block), pl.lds, s, q, k, v, (uint16_t*)p.out, p.N, p.H, p.F * p.H, p.ldq, p.ldkv,
+                       0.125f);
+  } else {
+    hipLaunchKernelGGL((attn_vit_long_kernel<T, NC>), dim3(pl.grid[0]), dim3(pl.block), 0, s, q, k, v, (uint16_t*)p.out, p.lse, p.N, p.H,
+                       p.ldq, p.ldkv, 0.125f);
   }
-  if (NQ != N) return VMC_E_SHAPE;
-  if (N == 577) return launch_full<T, 577>(q, k, v, ldq, ldkv, out, lse, F, N, H, s);
-  return launch_full<T, 0>(q, k, v, ldq, ldkv, out, lse, F, N, H, s);
+  VMC_CHECK_LAUNCH();
+  return 0;
 }
 
 }  // namespace
 
-// Entry point for attention.hip's dispatch_vit (not part of the C ABI): N > 288 keys, NQ = N (full) or 1 (class query; lse unused).
-// The caller has checked pointers and alignment.
-__attribute__((visibility("hidden"))) int attn_vit_long_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, size_t ldq, size_t ldkv,
-                                                            int NQ, void* out, float* lse, int F, int N, int H, int dtype16, hipStream_t s) {
-  if (dtype16 == VMC_BF16) return dispatch<BF16>(q, k, v, ldq, ldkv, NQ, out, lse, F, N, H, s);
-  if (dtype16 == VMC_F16) return dispatch<F16>(q, k, v, ldq, ldkv, NQ, out, lse, F, N, H, s);
-  return VMC_E_DTYPE;
+// The executor of attn_route.h's ATTN_VIT_LONG / ATTN_VIT_LONG_CLS plans (declared in common.h).
+int attn_vit_long_fwd(const AttnPlan& pl, const AttnVitProblem& p, hipStream_t s) {
+  if (p.dtype16 == VMC_BF16) return pl.nc == ATT_VL_NC ? launch<BF16, ATT_VL_NC>(pl, p, s) : launch<BF16, 0>(pl, p, s);
+  return pl.nc == ATT_VL_NC ? launch<F16, ATT_VL_NC>(pl, p, s) : launch<F16, 0>(pl, p, s);
 }

@@ -37,6 +37,16 @@ static inline int set_max_lds(bool& done, int bytes, K... kernels) {
   return 0;
 }
 
+// Executors of attn_route.h's plans for the streamed ViT kernels (attention_vit_long.hip) and the tiled masked ones
+// (attention_long.hip), called by attention.hip (not part of the C ABI).
+struct AttnPlan;
+struct AttnVitProblem;
+struct AttnFwdProblem;
+struct AttnBwdProblem;
+__attribute__((visibility("hidden"))) int attn_vit_long_fwd(const AttnPlan& plan, const AttnVitProblem& p, hipStream_t s);
+__attribute__((visibility("hidden"))) int attn_long_fwd(const AttnPlan& plan, const AttnFwdProblem& p, hipStream_t s);
+__attribute__((visibility("hidden"))) int attn_long_bwd(const AttnPlan& plan, const AttnBwdProblem& p, hipStream_t s);
+
 // ---- 16-bit element traits ---------------------------------------------------------------------
 struct BF16 {
   static constexpr int id = VMC_BF16;
