@@ -305,6 +305,10 @@ int vmc_act_bwd(const void* x, const void* dy, void* dx, size_t n, int act, int 
  * models/student_model.py:93).  x f32 or 16-bit, out16 and/or out32. */
 int vmc_mean_pool(const void* x, void* out16, float* out32, int B, int T, int D, int x_dtype, int dtype16,
                   void* stream);
+/* The same over the first n = *pool_len rows of every clip (see "POOL LENGTH" below; the row stride stays T):
+ * out[b, :] = (1/n) sum_{t<n} x[b, t, :].  pool_len == NULL: vmc_mean_pool (which is this entry with NULL). */
+int vmc_mean_pool_len(const void* x, void* out16, float* out32, int B, int T, int D, const int* pool_len, int x_dtype,
+                      int dtype16, void* stream);
 /* x[b,t,:] += pe[t,:]  sinusoidal positional encoding of TFAM/models/AMO_CLIP.py:88-97 (f32 in place). */
 int vmc_add_sinusoidal_pe(float* x, int B, int T, int D, void* stream);
 /* y = a + alpha * b elementwise, f32. */
@@ -316,6 +320,9 @@ int vmc_add(const void* a, const void* b, void* y, size_t n, int a_dtype, int b_
 /* Backward of vmc_mean_pool: dx[b,t,:] = dout[b,:] / T. */
 int vmc_mean_pool_bwd(const void* dout, void* dx, int B, int T, int D, int dout_dtype, int dx_dtype, int dtype16,
                       void* stream);
+/* Backward of vmc_mean_pool_len: dx[b,t,:] = dout[b,:] / n for t < n and 0 for n <= t < T (every row of dx is written). */
+int vmc_mean_pool_bwd_len(const void* dout, void* dx, int B, int T, int D, const int* pool_len, int dout_dtype, int dx_dtype,
+                          int dtype16, void* stream);
 /* Training-path token assembly of K1 (class token concat + positional embedding, OpenAI clip
  * VisionTransformer.forward): x[f,0,:] = cls + pos[0]; x[f,1+p,:] = xp[f*(N-1)+p,:] + pos[1+p].
  * xp 16-bit [F*(N-1), D]; cls f32 [D]; pos f32 [N,D]; x [F*N, D] f32 or 16-bit. */
@@ -405,10 +412,17 @@ int vmc_tfam_layer_fwd(const float* x_in, const uint8_t* mask, const uint8_t* ma
 /* logits[B, C] (fp32) = classifier(mean over all T rows of LN_ffn(last layer))  (AMO_CLIP.py:84,:170). */
 int vmc_tfam_head_fwd(const void* wpack, const float* ppack, float* logits, void* workspace, size_t workspace_bytes,
                       int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int dtype16, void* stream);
+/* The same with the mean over the first *pool_len rows of every clip ("POOL LENGTH" below); same launches. */
+int vmc_tfam_head_fwd_len(const void* wpack, const float* ppack, float* logits, void* workspace, size_t workspace_bytes,
+                          int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, const int* pool_len, int dtype16,
+                          void* stream);
 /* kv + L layers + head in one call (AMO_CLIP.forward, :99-171, eval mode). */
 int vmc_tfam_forward(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const void* wpack,
                      const float* ppack, float* logits, void* workspace, size_t workspace_bytes, int B, int T, int Tk,
                      int D, int H, int ff, int L, int C, int has_cross, int dtype16, void* stream);
+int vmc_tfam_forward_len(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const void* wpack,
+                         const float* ppack, float* logits, void* workspace, size_t workspace_bytes, int B, int T, int Tk,
+                         int D, int H, int ff, int L, int C, int has_cross, const int* pool_len, int dtype16, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K11-K14 fused, TRAINING — forward + backward of the TFAM block for short clips as two launch chains
@@ -452,6 +466,9 @@ typedef struct vmc_tfam_head_params {
 } vmc_tfam_head_params;
 /* Saved activations + backward scratch of one step of B clips; caller-owned, must stay untouched between fwd and bwd. */
 size_t vmc_tfam_train_workspace_bytes(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross);
+/* Byte offset, inside that workspace, of the fp32 [B*T, D] gradient wrt the last layer's output that vmc_tfam_head_bwd leaves there
+ * (the mean-pool's backward; the layer chain only reads it).  -1 for an unsupported shape. */
+long long vmc_tfam_train_pool_grad_offset(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross);
 /* AttentionLayer.forward in train mode.  layers = all L structs (layer l > 0 reads layer l-1's norm_ffn);  x_in: the fp32 tokens
  * (layer 0; NULL otherwise); motion: raw fp32 motion tokens [B*Tk, D] (has_cross).  seeds: the 7 seeds of THIS layer. */
 int vmc_tfam_layer_train_fwd(const float* x_in, const float* motion, const uint8_t* mask, const uint8_t* mask_kv,
@@ -462,11 +479,19 @@ int vmc_tfam_layer_train_fwd(const float* x_in, const float* motion, const uint8
 int vmc_tfam_head_train_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits,
                             void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
                             int has_cross, float p_mlp, uint64_t seed, int dtype16, void* stream);
+int vmc_tfam_head_train_fwd_len(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits,
+                                void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
+                                int has_cross, float p_mlp, uint64_t seed, const int* pool_len, int dtype16, void* stream);
 /* Backward of the head: from dlogits fp32 [B, C] to the gradient wrt the last layer's output (left in the workspace) and
  * the classifier's parameter gradients (autograd of AMO_CLIP.py:170-171). */
 int vmc_tfam_head_bwd(const float* dlogits, const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head,
                       void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
                       int has_cross, float p_mlp, uint64_t seed, int dtype16, void* stream);
+/* With a pool length the gradient is dpooled / n on the rows t < n of every clip and 0 on the rows n..T-1; it is the input of the
+ * last layer's first dgrad launch, so those rows stay zero down the whole backward chain.  Same *pool_len as the forward. */
+int vmc_tfam_head_bwd_len(const float* dlogits, const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head,
+                          void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
+                          int has_cross, float p_mlp, uint64_t seed, const int* pool_len, int dtype16, void* stream);
 /* Backward of one AttentionLayer (autograd of AMO_CLIP.py:37-51): consumes the gradient wrt its output from the workspace,
  * leaves the gradient wrt its input there for layer-1 (not computed for layer 0: the tokens need no gradient), writes the
  * layer's parameter gradients.  x_in (layer 0 only) is not read: its 16-bit cast was saved by the forward. */
@@ -482,6 +507,15 @@ int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, const uint8_t*
                        const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D,
                        int H, int ff, int L, int C, int has_cross, float p_drop, float p_mlp,
                        const uint64_t* seeds, int dtype16, void* stream);
+/* The whole chains with a pool length (the `_len` head entries above in place of the plain ones; same launches). */
+int vmc_tfam_train_fwd_len(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv,
+                           const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits, void* workspace,
+                           size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross,
+                           float p_drop, float p_mlp, const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
+int vmc_tfam_train_bwd_len(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
+                           const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D,
+                           int H, int ff, int L, int C, int has_cross, float p_drop, float p_mlp,
+                           const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K15 — fused Adam / AdamW over one flat fp32 buffer (train.py:66; TFAM/train_and_eval.py:53).
@@ -497,7 +531,15 @@ int vmc_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
  * vmc_train_tick: t += 1, recomputes hyper[1..2] and the n_seeds seeds (splitmix of base seed, t and the index); enqueue it once
  * per step before the forward.  vmc_adam_step_dev = vmc_adam_step reading its four scalars from `hyper`.
  * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd): a value < 2^63 is the seed itself; with bit
- * 63 set the low 63 bits are the ADDRESS of a u64 in device memory holding it (e.g. &state[2 + i]), read at kernel start. */
+ * 63 set the low 63 bits are the ADDRESS of a u64 in device memory holding it (e.g. &state[2 + i]), read at kernel start.
+ * POOL LENGTH (the `_len` entries: vmc_mean_pool_len / _bwd_len, vmc_tfam_head_fwd_len, vmc_tfam_forward_len,
+ * vmc_tfam_head_train_fwd_len, vmc_tfam_head_bwd_len, vmc_tfam_train_fwd_len / _bwd_len): the same idea for the mean-pool.
+ * `pool_len` points to ONE int32 in DEVICE memory, n = the number of leading rows of every clip that enter the mean, read at
+ * kernel start -- a captured launch pools over the n of the replay, so one graph serves every batch that was zero-padded (tokens
+ * and key masks) from its own length n up to the captured T and gives the unpadded batch's logits and gradients (the reference
+ * pools over the batch's padded length, TFAM/models/AMO_CLIP.py:169-170; every other operation is per row or masks the added
+ * keys).  The host cannot validate device memory: kernels clamp n into [1, T].  NULL = T, i.e. the entry without the suffix,
+ * which is implemented as that call: one kernel body per pool, the same launches either way. */
 int vmc_train_tick(void* state, float* hyper, float beta1, float beta2, int n_seeds, void* stream);
 int vmc_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
                       float eps, float weight_decay, int decoupled_wd, void* stream);

@@ -6,7 +6,8 @@
 ``projection_layer.*``; TFAM/models/AMO_CLIP.py:19-34,81-86) so its checkpoints load ``strict=True``.
 
 Reference behaviours kept on purpose: the mean-pool runs over ALL T rows
-including padded ones (:170); with ``use_pe`` the positional encoding is added IN PLACE to the caller's
+including padded ones (:170) -- ``forward(..., pool_len=n)`` is how a batch that was zero-padded beyond its own
+length (to share a captured graph, graphs.pad_to_bucket) keeps that mean: the pool then takes rows 0..n-1; with ``use_pe`` the positional encoding is added IN PLACE to the caller's
 tensors (:133-134); the FFN activation is ReLU whatever ``activation`` says (:13,81), the classifier uses
 exact GELU; in cross-attention mode every layer attends the same raw motion tokens.
 
@@ -282,7 +283,7 @@ class AMO_CLIP(nn.Module):
             return None
         return _f32c(x), m, (_f32c(motion) if cross else None), m_kv, cross
 
-    def _forward_fused(self, rgb_emb, motion_emb, m_rgb, m_flow):
+    def _forward_fused(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None):
         """Eval forward through vmc_tfam_forward (one call: hoisted K|V GEMM + 6 launches per layer + pool + head).
         Returns None when the shapes are outside the fused chain's set; the per-op path below then runs."""
         from ... import tfam_fused as tf
@@ -291,9 +292,9 @@ class AMO_CLIP(nn.Module):
             return None
         x, m, motion, m_kv, cross = sel
         pack = tf.get_pack(self, self.compute_dtype).refresh()
-        return pack.forward(x, motion, m, m_kv, cross, slot=getattr(self, "fused_slot", 0))
+        return pack.forward(x, motion, m, m_kv, cross, slot=getattr(self, "fused_slot", 0), pool_len=pool_len)
 
-    def _forward_fused_train(self, rgb_emb, motion_emb, m_rgb, m_flow):
+    def _forward_fused_train(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None):
         """Train-mode forward + (through autograd) backward as the fused launch chains of tfam_train.py: one autograd node for the
         whole model.  None when the mode / shapes are outside the chain's set."""
         from ... import tfam_train as tt
@@ -301,11 +302,31 @@ class AMO_CLIP(nn.Module):
         if sel is None:
             return None
         x, m, motion, m_kv, cross = sel
-        return tt.forward_train(self, x, motion, m, m_kv, cross, self._next_seed)
+        return tt.forward_train(self, x, motion, m, m_kv, cross, self._next_seed, pool_len=pool_len)
 
-    def forward(self, rgb_emb, motion_emb, mask_rgb=None, mask_flow=None):
+    @property
+    def pools_padded_tokens(self) -> bool:
+        """True for the fusion modes whose pooled stream may be zero-padded further under ``pool_len`` (cross attention, rgb-only,
+        flow-only).  The two concatenation modes drop "the last padded position" with ``rgb_emb[:, :-1]`` (:153-154): more padding
+        would change which row is dropped, so they take exact shapes only."""
+        return bool(self.use_only_rgb or self.use_only_flow or self.use_cross_attention)
+
+    def forward(self, rgb_emb, motion_emb, mask_rgb=None, mask_flow=None, *, pool_len=None):
+        """The reference's four arguments, plus ``pool_len`` (None | int | one-element int32 device tensor): the logical length of
+        the stream that is pooled (RGB tokens in cross and rgb-only mode, motion tokens in flow-only mode).  The classifier then
+        sees the mean over rows 0..pool_len-1 of every clip instead of all T rows, and rows pool_len..T-1 receive a zero
+        gradient: with the added rows masked as keys (mask_rgb / mask_flow 0 there), a batch zero-padded from length pool_len to T
+        gives the logits and gradients of the unpadded batch.  The kernels read the value from device memory, so a captured
+        forward or step pools over the value of each replay; an int becomes a device tensor here (not allowed while capturing).
+        Dropout masks are indexed by the PADDED shape (element ``row * N + col`` of the padded tensors): a padded step draws
+        other masks than the unpadded one, and the same masks as an eager step on the same padded tensors."""
         dt16, D = self.compute_dtype, self.d_model
         dev = self.device
+        if pool_len is not None:
+            if not self.pools_padded_tokens:
+                raise ValueError("pool_len is not supported with the concatenation fusion modes (use_cross_attention=False without "
+                                 "use_only_rgb / use_only_flow): they drop the last padded RGB position, which further padding moves")
+            pool_len = ops.pool_len_tensor(pool_len, rgb_emb.device if rgb_emb.is_cuda else dev)
         rgb_emb = rgb_emb if rgb_emb.is_cuda else rgb_emb.to(dev)
         motion_emb = motion_emb if motion_emb.is_cuda else motion_emb.to(dev)
         if self.use_pe:                                   # in place on the caller's tensors, as the reference (:133-134)
@@ -316,11 +337,11 @@ class AMO_CLIP(nn.Module):
         seed_fn = self._next_seed
         self._seed_site = -1                              # device-seed mode: call sites are numbered from 0 in every forward
         if self.fused_inference and not self.training and not torch.is_grad_enabled():
-            out = self._forward_fused(rgb_emb, motion_emb, m_rgb, m_flow)
+            out = self._forward_fused(rgb_emb, motion_emb, m_rgb, m_flow, pool_len)
             if out is not None:
                 return out
         if self.fused_training and self.training and torch.is_grad_enabled():
-            out = self._forward_fused_train(rgb_emb, motion_emb, m_rgb, m_flow)
+            out = self._forward_fused_train(rgb_emb, motion_emb, m_rgb, m_flow, pool_len)
             if out is not None:
                 return out
             self._seed_site = -1                          # nothing was drawn on a path that declined
@@ -360,7 +381,7 @@ class AMO_CLIP(nn.Module):
             x, x16 = pair(x)
             for layer in self.layers:
                 x, x16 = layer.run(x, x16, B, T, dt16, m, seed_fn=seed_fn)
-        pooled = ag.MeanPoolFn.apply(x, B, T, dt16, True)                                      # [B, D] f32, all T rows
+        pooled = ag.MeanPoolFn.apply(x, B, T, dt16, True, pool_len)                            # [B, D] f32, all T rows (or pool_len)
         h = ag.layernorm(pooled, self.classifier[0].weight, self.classifier[0].bias, dt16)
         h = ag.linear(h, self.classifier[1].weight, self.classifier[1].bias, act=ops.ACT_GELU_ERF)
         h = ag.dropout(h, self.mlp_dropout, self.training, seed_fn)

@@ -36,6 +36,7 @@ class Config:
         self.use_cross_attention, self.use_only_rgb, self.use_only_flow, self.use_pe, self.concat_dim = True, False, False, False, 1
         self.dropout, self.mlp_dropout, self.device, self.checkpoint_dir, self.log_dir = 0.1, 0.1, "cuda", "checkpoints", "logs"
         self.task, self.motion_key, self.use_graphs = "multilabel", "flow", False    # use_graphs: hipGraph replay of the eval forward
+        self.graph_bucket = 1      # use_graphs with ragged loaders: pad clip lengths to multiples of this, one graph per bucket (graphs.pad_to_bucket)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
 
@@ -61,6 +62,8 @@ class Config:
                   mlp_dropout=m["mlp_dropout"], use_pe=m["use_pe"], use_only_rgb=m["use_only_rgb"], use_only_flow=m["use_only_flow"])
         if "frame_diff_dataset_path" in d:
             kw["motion_key"] = "frame_diff"
+        if "graph_bucket" in t:                     # not a key of the reference's YAML: optional
+            kw["graph_bucket"] = int(t["graph_bucket"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -98,14 +101,22 @@ def _model_forward(model, batch, config):
 
 class GraphedEvalForward:
     """Evaluation forward as hipGraph replays.  At the reference's batch size (8 clips) a forward is ~90 kernels of a few
-    microseconds: launch bound.  One graph per distinct (B, T_rgb, T_motion) shape, captured on first sight; the reference
-    pools with ``x.mean(dim=1)`` over the padded length (AMO_CLIP.py:169), so a batch cannot be padded further to share a
-    graph without changing its logits -- ``bucket`` therefore defaults to 1 (exact shapes: fixed-length loaders, e.g.
-    ``num_frames=16``, replay one graph; ragged loaders fill ``max_graphs`` and fall back to eager launches).  Only for
+    microseconds: launch bound.  One graph per distinct (B, T_rgb, T_motion) shape, captured on first sight.  ``bucket = 1``
+    (the default) keys on exact shapes: fixed-length loaders, e.g. ``num_frames=16``, replay one graph; ragged loaders fill
+    ``max_graphs`` and fall back to eager launches.  ``bucket > 1`` pads every batch to the next multiple of ``bucket`` (RGB and
+    motion tokens each to their own) and shares one graph per padded shape.  The reference pools with ``x.mean(dim=1)`` over the
+    batch's own padded length (AMO_CLIP.py:169), so the padded batch carries that length as ``pool_len`` -- a device value the
+    captured pool kernel reads at replay time -- and its logits are those of the unpadded batch (graphs.pad_to_bucket; up to
+    the kernel choice the other length implies, i.e. within the usual tolerance rather than bit for bit).  The concatenation
+    modes cannot be padded (AMO_CLIP.pools_padded_tokens) and keep exact shapes whatever ``bucket`` says.  Only for
     ``model.eval()`` under ``no_grad`` (no dropout, no optimiser state inside the graph)."""
 
     def __init__(self, model, config, bucket=1, max_graphs=32, streams=2):
-        self.model, self.config, self.bucket, self.max_graphs = model, config, bucket, max_graphs
+        from ..graphs import _PoolLens, pooled_stream
+        self.model, self.config, self.max_graphs = model, config, max_graphs
+        self.pooled = pooled_stream(model)
+        self.bucket = int(bucket) if self.pooled is not None else 1
+        self._lens = _PoolLens()
         self._graphs = {}
         # Two batches in flight: an evaluation loop's batches are independent, and at the reference batch size a forward is a
         # chain of ~27 dependent launches of ~4 us fixed cost each, so a second stream's forward fills the first one's launch
@@ -115,31 +126,32 @@ class GraphedEvalForward:
         self._free = [None] * len(self._streams)       # event: the consumer has copied this slot's previous output
         self._rr = -1
 
-    def _pad(self, x, T):
-        if x.shape[1] == T:
-            return x
-        out = torch.zeros((x.shape[0], T) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
-        out[:, :x.shape[1]] = x
-        return out
-
     def _run(self, batch, slot):
-        from ..graphs import GraphedCallable
-        dev, mk, bk = self.config.device, self.config.motion_key, self.bucket
+        from ..graphs import GraphedCallable, pad_to_bucket
+        dev, mk = self.config.device, self.config.motion_key
         rgb, mot = batch["embeddings"].to(dev), batch[f"{mk}_embeddings"].to(dev)
         mr, mf = batch["mask_rgb"].to(dev), batch[f"mask_{mk}"].to(dev)
-        Tr, Tf = -(-rgb.shape[1] // bk) * bk, -(-mot.shape[1] // bk) * bk
-        key = (slot, rgb.shape[0], Tr, Tf, rgb.shape[2])
+        rgb, mot, mr, mf, n = pad_to_bucket(rgb, mot, mr, mf, self.bucket, self.pooled)
+        key = (slot, rgb.shape[0], rgb.shape[1], mot.shape[1], rgb.shape[2])
         self.model.fused_slot = slot
-        if key not in self._graphs and len(self._graphs) >= self.max_graphs * len(self._streams):
-            return self.model(rgb, mot, mask_rgb=mr, mask_flow=mf)              # too many shapes: eager
-        rgb, mot, mr, mf = self._pad(rgb, Tr), self._pad(mot, Tf), self._pad(mr, Tr), self._pad(mf, Tf)
-        g = self._graphs.get(key)
-        if g is None:
+        if n is None:                                   # exact shapes
+            args = (rgb, mot, mr, mf)
+
             def fwd(a, b, c, d):
                 with torch.no_grad():
                     return self.model(a, b, mask_rgb=c, mask_flow=d)
-            g = self._graphs[key] = GraphedCallable(fwd, rgb, mot, mr, mf)
-        return g(rgb, mot, mr, mf)
+        else:
+            args = (rgb, mot, mr, mf, self._lens.get(n, rgb.device))
+
+            def fwd(a, b, c, d, e):
+                with torch.no_grad():
+                    return self.model(a, b, mask_rgb=c, mask_flow=d, pool_len=e)
+        g = self._graphs.get(key)
+        if g is None:
+            if len(self._graphs) >= self.max_graphs * len(self._streams):
+                return fwd(*args)                       # too many shapes: eager
+            g = self._graphs[key] = GraphedCallable(fwd, *args)
+        return g(*args)
 
     def launch(self, batch):
         """Start the forward of `batch` on the next slot's stream; returns a handle for ``result``.  Launch batch k+1 before
@@ -198,19 +210,21 @@ class ModelTrainer:
         self.optimizer = FusedAdam(self.arena, lr=1e-4, weight_decay=0.1, decoupled=True)       # lr hard-coded as :53
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=config.epochs, eta_min=1e-6)
         self.reducer = parallel.GradientAllReducer(self.arena.flat_grad).attach(self.arena)   # buckets go out during the backward
-        self._graphed_eval = GraphedEvalForward(model, config) if getattr(config, "use_graphs", False) else None
+        bucket = int(getattr(config, "graph_bucket", 1))
+        self._graphed_eval = GraphedEvalForward(model, config, bucket=bucket) if getattr(config, "use_graphs", False) else None
         self._graphed_train = None
         if getattr(config, "use_graphs", False):
             # captured training steps: step count / lr / dropout seeds in device memory (optim.FusedAdam.enable_device_state).
             # One process: the whole step is one graph.  Data parallel: forward + backward graph, the gradient exchange, optimiser graph.
-            from ..graphs import GraphedTrainStep
+            from ..graphs import GraphedTrainStep, pooled_stream
+            ragged = dict(bucket=bucket, pooled=pooled_stream(model))
             self.optimizer.enable_device_state(base_seed=config.seed if world == 1 else config.seed * 1000 + rank)
             model.use_device_seeds(self.optimizer)
             if world == 1:
-                self._graphed_train = GraphedTrainStep(self._device_state_step, self.optimizer)
+                self._graphed_train = GraphedTrainStep(self._device_state_step, self.optimizer, **ragged)
             else:
                 self._graphed_train = GraphedTrainStep(self._device_state_fwd_bwd, self.optimizer, exchange=self.reducer.all_reduce,
-                                                       opt_fn=self.optimizer.step)
+                                                       opt_fn=self.optimizer.step, **ragged)
         if world == 1 and os.environ.get("VMC_ADAM_OVERLAP", "0") == "1":
             # AdamW of a finished layer on a side stream beside the backward of the layers below it.  Bit-identical, but measured
             # SLOWER on MI355X (captured B = 8 step 0.88 -> 0.95-1.01 ms: the fork / join edges of a multi-stream hipGraph cost more
@@ -221,21 +235,22 @@ class ModelTrainer:
     def _forward(self, batch):
         return _model_forward(self.model, batch, self.config), batch["labels"].to(self.config.device)
 
-    def _device_state_step(self, rgb, mot, mr, mf, labels):
-        """tick + forward + loss + backward + AdamW with every step-dependent scalar read from device memory."""
+    def _device_state_step(self, rgb, mot, mr, mf, labels, pool_len=None):
+        """tick + forward + loss + backward + AdamW with every step-dependent scalar read from device memory (pool_len: the
+        bucketed batch's own length, GraphedTrainStep)."""
         from ..losses import loss_and_grad
         self.optimizer.tick()
-        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf)
+        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)      # criterion(output, labels); loss.backward() (:81-83)
         output.backward(dlogits)
         self.optimizer.step()
         return loss, output.detach()
 
-    def _device_state_fwd_bwd(self, rgb, mot, mr, mf, labels):
+    def _device_state_fwd_bwd(self, rgb, mot, mr, mf, labels, pool_len=None):
         """The data-parallel step's first graph: tick + forward + loss + backward (the exchange and AdamW follow outside it)."""
         from ..losses import loss_and_grad
         self.optimizer.tick()
-        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf)
+        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)
         output.backward(dlogits)
         return loss, output.detach()
@@ -318,7 +333,8 @@ class ModelTester:
     def __init__(self, model, test_set, config, rank=0, world=1):
         self.model, self.test_set, self.config, self.rank, self.world = model, test_set, config, rank, world
         _, self.mAP_metric = task_objects(config)
-        self._graphed_eval = GraphedEvalForward(model, config) if getattr(config, "use_graphs", False) else None
+        self._graphed_eval = (GraphedEvalForward(model, config, bucket=int(getattr(config, "graph_bucket", 1)))
+                              if getattr(config, "use_graphs", False) else None)
 
     def load_best_model(self, checkpoint_dir):
         """:186-191 — weights-only load of ``best_model.pth`` (keys with or without the DataParallel ``module.`` prefix)."""

@@ -55,6 +55,7 @@ SIGNATURES = {
     "vmc_scale_by_device_scalar": (I, [P, P, Z, P, P]),
     "vmc_add": (I, [P, P, P, Z, I, I, I, I, P]),
     "vmc_mean_pool_bwd": (I, [P, P, I, I, I, I, I, I, P]),
+    "vmc_mean_pool_bwd_len": (I, [P, P, I, I, I, P, I, I, I, P]),
     "vmc_assemble_tokens": (I, [P, P, P, P, I, I, I, I, I, P]),
     "vmc_dropout": (I, [P, P, Z, F, ctypes.c_uint64, I, I, P]),
     "vmc_cast_dropout2": (I, [P, P, ctypes.c_size_t, F, ctypes.c_uint64, F, ctypes.c_uint64, I, P]),
@@ -67,6 +68,7 @@ SIGNATURES = {
     "vmc_act_fwd": (I, [P, P, Z, I, I, P]),
     "vmc_act_bwd": (I, [P, P, P, Z, I, I, P]),
     "vmc_mean_pool": (I, [P, P, P, I, I, I, I, I, P]),
+    "vmc_mean_pool_len": (I, [P, P, P, I, I, I, P, I, I, P]),
     "vmc_add_sinusoidal_pe": (I, [P, I, I, I, P]),
     "vmc_axpby_f32": (I, [P, P, P, Z, F, F, P]),
     "vmc_cast_f32_to_16": (I, [P, P, Z, I, P]),
@@ -81,14 +83,21 @@ SIGNATURES = {
     "vmc_tfam_kv_fwd": (I, [P, P, P, P, Z, I, I, I, I, I, I, I, I, I, P]),
     "vmc_tfam_layer_fwd": (I, [P, P, P, P, P, I, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
     "vmc_tfam_head_fwd": (I, [P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
+    "vmc_tfam_head_fwd_len": (I, [P, P, P, P, Z, I, I, I, I, I, I, I, I, I, P, I, P]),
     "vmc_tfam_forward": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
+    "vmc_tfam_forward_len": (I, [P, P, P, P, P, P, P, P, Z, I, I, I, I, I, I, I, I, I, P, I, P]),
     "vmc_tfam_train_workspace_bytes": (Z, [I] * 9),
+    "vmc_tfam_train_pool_grad_offset": (ctypes.c_longlong, [I] * 9),
     "vmc_tfam_layer_train_fwd": (I, [P, P, P, P, P, I, P, Z] + [I] * 9 + [F, P, I, P]),
     "vmc_tfam_head_train_fwd": (I, [P, P, P, P, Z] + [I] * 9 + [F, ctypes.c_uint64, I, P]),
     "vmc_tfam_head_bwd": (I, [P, P, P, P, Z] + [I] * 9 + [F, ctypes.c_uint64, I, P]),
+    "vmc_tfam_head_train_fwd_len": (I, [P, P, P, P, Z] + [I] * 9 + [F, ctypes.c_uint64, P, I, P]),
+    "vmc_tfam_head_bwd_len": (I, [P, P, P, P, Z] + [I] * 9 + [F, ctypes.c_uint64, P, I, P]),
     "vmc_tfam_layer_bwd": (I, [P, P, P, I, P, Z] + [I] * 9 + [F, P, I, P]),
     "vmc_tfam_train_fwd": (I, [P, P, P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, I, P]),
     "vmc_tfam_train_bwd": (I, [P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, I, P]),
+    "vmc_tfam_train_fwd_len": (I, [P, P, P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, P, I, P]),
+    "vmc_tfam_train_bwd_len": (I, [P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, P, I, P]),
     "vmc_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, I, F, P]),
     "vmc_train_tick": (I, [P, P, F, F, I, P]),
     "vmc_adam_step_dev": (I, [P, P, P, P, Z, P, F, F, F, F, I, P]),

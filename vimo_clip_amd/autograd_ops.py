@@ -624,13 +624,15 @@ class AddFn(torch.autograd.Function):
 
 
 class MeanPoolFn(torch.autograd.Function):
-    """[B*T, D] -> [B, D] mean over T (all rows, padded ones included: TFAM/models/AMO_CLIP.py:170)."""
+    """[B*T, D] -> [B, D] mean over T (all rows, padded ones included: TFAM/models/AMO_CLIP.py:170), or -- pool_len given, a
+    one-element int32 device tensor -- over the first pool_len rows of every clip; the backward then writes zeros to the rest."""
 
     @staticmethod
-    def forward(ctx, x, B, T, dt16, out_f32):
+    def forward(ctx, x, B, T, dt16, out_f32, pool_len=None):
         D = x.shape[-1]
-        o16, o32 = ops.mean_pool(x, B, T, D, dt16, out16=not out_f32, out32=out_f32)
+        o16, o32 = ops.mean_pool(x, B, T, D, dt16, out16=not out_f32, out32=out_f32, pool_len=pool_len)
         ctx.meta = (B, T, D, x.dtype, dt16)
+        ctx.pool_len = pool_len
         return o32 if out_f32 else o16
 
     @staticmethod
@@ -638,8 +640,9 @@ class MeanPoolFn(torch.autograd.Function):
         B, T, D, xdtype, dt16 = ctx.meta
         dout = dout.contiguous()
         dx = torch.empty((B * T, D), dtype=xdtype, device=dout.device)
-        check(lib.vmc_mean_pool_bwd(ptr(dout), ptr(dx), B, T, D, dt(dout), dt(dx), dt(dt16), stream()), "mean_pool_bwd")
-        return dx, None, None, None, None
+        check(lib.vmc_mean_pool_bwd_len(ptr(dout), ptr(dx), B, T, D, ptr(ctx.pool_len), dt(dout), dt(dx), dt(dt16), stream()),
+              "mean_pool_bwd")
+        return dx, None, None, None, None, None
 
 
 class AssembleTokensFn(torch.autograd.Function):

@@ -153,6 +153,13 @@ __device__ inline uint32_t hash32(uint64_t seed, uint64_t i) {
 __device__ inline uint64_t resolve_seed(uint64_t s) {
   return (s & VMC_SEED_IS_PTR) ? *(const uint64_t*)(uintptr_t)(s & ~VMC_SEED_IS_PTR) : s;
 }
+// Pool-length arguments of the ABI (include/vmc.h "POOL LENGTH"): a pointer to one int32 in device memory, read at kernel start so
+// that a captured launch sees the value of the replay; clamped into [1, Tn] (the host cannot validate device memory); NULL = Tn.
+__device__ inline int pool_rows(const int* __restrict__ pool_len, int Tn) {
+  if (pool_len == nullptr) return Tn;
+  const int n = *pool_len;
+  return n < 1 ? 1 : (n > Tn ? Tn : n);
+}
 __device__ inline float dropout_factor(float p, uint64_t seed, uint64_t i) {
   if (p <= 0.f) return 1.0f;
   return hash32(seed, i) >= (uint32_t)((double)p * 4294967296.0) ? 1.0f / (1.0f - p) : 0.0f;

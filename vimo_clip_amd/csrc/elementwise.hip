@@ -770,14 +770,15 @@ extern "C" int vmc_act_bwd(const void* x, const void* dy, void* dx, size_t n, in
 // ---- mean over T ----------------------------------------------------------------------------------
 template <typename T>
 __global__ void mean_pool_kernel(const void* __restrict__ x, uint16_t* __restrict__ o16, float* __restrict__ o32, int B, int Tn, int D,
-                                 int x_f32) {
+                                 int x_f32, const int* __restrict__ pool_len) {
   const size_t total = (size_t)B * D;
-  const float inv = 1.0f / (float)Tn;
+  const int np = pool_rows(pool_len, Tn);      // rows 0..np-1 of every clip enter the mean; the row stride stays Tn
+  const float inv = 1.0f / (float)np;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int d = (int)(i % D);
     const size_t b = i / D;
     float a = 0.f;
-    for (int t = 0; t < Tn; ++t) {
+    for (int t = 0; t < np; ++t) {
       const size_t idx = (b * Tn + t) * D + d;
       a += x_f32 ? ((const float*)x)[idx] : T::to_f32(((const uint16_t*)x)[idx]);
     }
@@ -786,14 +787,19 @@ __global__ void mean_pool_kernel(const void* __restrict__ x, uint16_t* __restric
     if (o32) o32[i] = a;
   }
 }
-extern "C" int vmc_mean_pool(const void* x, void* out16, float* out32, int B, int Tn, int D, int x_dtype, int dtype16, void* stream) {
+extern "C" int vmc_mean_pool_len(const void* x, void* out16, float* out32, int B, int Tn, int D, const int* pool_len, int x_dtype, int dtype16,
+                                 void* stream) {
   if (!x || (!out16 && !out32) || B <= 0 || Tn <= 0 || D <= 0) return VMC_E_ARG;
   const int grid = grid_for((size_t)B * D, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(mean_pool_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(mean_pool_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32);
+  if (dtype16 == VMC_F16) hipLaunchKernelGGL(mean_pool_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32, pool_len);
+  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(mean_pool_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32, pool_len);
   else return VMC_E_DTYPE;
   VMC_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int vmc_mean_pool(const void* x, void* out16, float* out32, int B, int Tn, int D, int x_dtype, int dtype16, void* stream) {
+  return vmc_mean_pool_len(x, out16, out32, B, Tn, D, nullptr, x_dtype, dtype16, stream);
 }
 
 // ---- sinusoidal positional encoding (TFAM/models/AMO_CLIP.py:88-97), added in place ---------------

@@ -30,20 +30,27 @@ extern "C" int vmc_add(const void* a, const void* b, void* y, size_t n, int a_dt
   VMC_DISPATCH16(add_kernel, grid_for(n, 256), a, b, y, n, a_dtype == VMC_F32, b_dtype == VMC_F32, y_dtype == VMC_F32)
 }
 
-// dx[b,t,:] = dout[b,:] / T   (backward of vmc_mean_pool)
+// dx[b,t,:] = dout[b,:] / n on the n pooled rows, 0 on rows n..T-1   (backward of vmc_mean_pool_len; n = T without a pool length)
 template <typename T>
-__global__ void mean_pool_bwd_kernel(const void* __restrict__ dout, void* __restrict__ dx, int B, int Tn, int D, int do_f32, int dx_f32) {
+__global__ void mean_pool_bwd_kernel(const void* __restrict__ dout, void* __restrict__ dx, int B, int Tn, int D, int do_f32, int dx_f32,
+                                     const int* __restrict__ pool_len) {
   const size_t total = (size_t)B * Tn * D;
-  const float inv = 1.0f / (float)Tn;
+  const int np = pool_rows(pool_len, Tn);
+  const float inv = 1.0f / (float)np;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const size_t b = i / ((size_t)Tn * D);
+    const int t = (int)((i / D) % Tn);
     const int d = (int)(i % D);
-    st1<T>(dx, i, dx_f32, ld1<T>(dout, b * D + d, do_f32) * inv);
+    st1<T>(dx, i, dx_f32, t < np ? ld1<T>(dout, b * D + d, do_f32) * inv : 0.f);
   }
 }
-extern "C" int vmc_mean_pool_bwd(const void* dout, void* dx, int B, int Tn, int D, int dout_dtype, int dx_dtype, int dtype16, void* stream) {
+extern "C" int vmc_mean_pool_bwd_len(const void* dout, void* dx, int B, int Tn, int D, const int* pool_len, int dout_dtype, int dx_dtype, int dtype16,
+                                     void* stream) {
   if (!dout || !dx || B <= 0 || Tn <= 0 || D <= 0) return VMC_E_ARG;
-  VMC_DISPATCH16(mean_pool_bwd_kernel, grid_for((size_t)B * Tn * D, 256), dout, dx, B, Tn, D, dout_dtype == VMC_F32, dx_dtype == VMC_F32)
+  VMC_DISPATCH16(mean_pool_bwd_kernel, grid_for((size_t)B * Tn * D, 256), dout, dx, B, Tn, D, dout_dtype == VMC_F32, dx_dtype == VMC_F32, pool_len)
+}
+extern "C" int vmc_mean_pool_bwd(const void* dout, void* dx, int B, int Tn, int D, int dout_dtype, int dx_dtype, int dtype16, void* stream) {
+  return vmc_mean_pool_bwd_len(dout, dx, B, Tn, D, nullptr, dout_dtype, dx_dtype, dtype16, stream);
 }
 
 // Token assembly (training path of K1): x[f,0,:] = cls + pos[0];  x[f,1+p,:] = xp[f*g2+p,:] + pos[1+p]

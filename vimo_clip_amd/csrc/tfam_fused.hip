@@ -262,12 +262,12 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
 }
 
 template <typename T>
-int tf_head_impl(const uint16_t* wp, const float* pp, float* logits, const TfDims& d, const TfWs& w, hipStream_t s) {
+int tf_head_impl(const uint16_t* wp, const float* pp, float* logits, const TfDims& d, const TfWs& w, const int* pool_len, hipStream_t s) {
   const int D = d.D;
   const float* lnf = pp + vmc_tfam_pack_offset(VMC_TFAM_P_NORM_FFN, d.L - 1, D, d.ff, d.L, d.C);
   const float* lnc = pp + vmc_tfam_pack_offset(VMC_TFAM_P_CLS_LN, 0, D, d.ff, d.L, d.C);
-  if (D == 768) hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f);
-  else hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f);
+  if (D == 768) hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f, pool_len);
+  else hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f, pool_len);
   VMC_CHECK_LAUNCH();
   int rc;
   {
@@ -343,20 +343,25 @@ extern "C" int vmc_tfam_layer_fwd(const float* x_in, const uint8_t* mask, const 
   return VMC_E_DTYPE;
 }
 
-extern "C" int vmc_tfam_head_fwd(const void* wpack, const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D,
-                                 int H, int ff, int L, int C, int has_cross, int dtype16, void* stream) {
+extern "C" int vmc_tfam_head_fwd_len(const void* wpack, const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D,
+                                     int H, int ff, int L, int C, int has_cross, const int* pool_len, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
   if (int rc = tf_check(d)) return rc;
   const TfWs w = tf_ws(ws, d);
   if (ws == nullptr || ws_bytes < w.bytes) return VMC_E_ARG;
-  if (dtype16 == VMC_BF16) return tf_head_impl<BF16>((const uint16_t*)wpack, ppack, logits, d, w, (hipStream_t)stream);
-  if (dtype16 == VMC_F16) return tf_head_impl<F16>((const uint16_t*)wpack, ppack, logits, d, w, (hipStream_t)stream);
+  if (dtype16 == VMC_BF16) return tf_head_impl<BF16>((const uint16_t*)wpack, ppack, logits, d, w, pool_len, (hipStream_t)stream);
+  if (dtype16 == VMC_F16) return tf_head_impl<F16>((const uint16_t*)wpack, ppack, logits, d, w, pool_len, (hipStream_t)stream);
   return VMC_E_DTYPE;
 }
 
-extern "C" int vmc_tfam_forward(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const void* wpack,
-                                const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D, int H, int ff,
-                                int L, int C, int has_cross, int dtype16, void* stream) {
+extern "C" int vmc_tfam_head_fwd(const void* wpack, const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D,
+                                 int H, int ff, int L, int C, int has_cross, int dtype16, void* stream) {
+  return vmc_tfam_head_fwd_len(wpack, ppack, logits, ws, ws_bytes, B, T, Tk, D, H, ff, L, C, has_cross, nullptr, dtype16, stream);
+}
+
+extern "C" int vmc_tfam_forward_len(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const void* wpack,
+                                    const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D, int H, int ff,
+                                    int L, int C, int has_cross, const int* pool_len, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
   if (int rc = tf_check(d)) return rc;
   if (!x || !wpack || !ppack || !logits || (has_cross && !motion)) return VMC_E_ARG;
@@ -371,5 +376,11 @@ extern "C" int vmc_tfam_forward(const float* x, const float* motion, const uint8
                                        : tf_layer_impl<F16>(xin, mask, mask_kv, (const uint16_t*)wpack, ppack, l, d, w, s, mkv);
     if (rc) return rc;
   }
-  return vmc_tfam_head_fwd(wpack, ppack, logits, ws, ws_bytes, B, T, Tk, D, H, ff, L, C, has_cross, dtype16, stream);
+  return vmc_tfam_head_fwd_len(wpack, ppack, logits, ws, ws_bytes, B, T, Tk, D, H, ff, L, C, has_cross, pool_len, dtype16, stream);
+}
+extern "C" int vmc_tfam_forward(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const void* wpack,
+                                const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D, int H, int ff,
+                                int L, int C, int has_cross, int dtype16, void* stream) {
+  return vmc_tfam_forward_len(x, motion, mask, mask_kv, wpack, ppack, logits, ws, ws_bytes, B, T, Tk, D, H, ff, L, C, has_cross, nullptr, dtype16,
+                              stream);
 }

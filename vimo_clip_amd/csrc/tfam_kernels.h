@@ -868,17 +868,20 @@ __global__ void __launch_bounds__(TF_NTH) tf_gemm_ring_kernel(const TfArgs a) {
 }
 
 // ---- mean-pool + the two LayerNorms of the tail: pooled16[b] = LN_cls(mean_t LN_ffn(y[b, t])) ------------------------------
+// The mean runs over the first pool_rows(pool_len, Tn) rows of every clip (common.h; NULL = all Tn rows); the row stride stays Tn.
 template <typename T, int D>
 __global__ void __launch_bounds__(256) tf_pool_kernel(const float* __restrict__ y, const float* __restrict__ g1, const float* __restrict__ b1,
                                                       const float* __restrict__ g2, const float* __restrict__ b2,
-                                                      uint16_t* __restrict__ out, int Tn, float eps, float* __restrict__ pooled32 = nullptr) {
+                                                      uint16_t* __restrict__ out, int Tn, float eps, const int* __restrict__ pool_len,
+                                                      float* __restrict__ pooled32 = nullptr) {
   constexpr int NI = D / 256;                    // float4 per lane per row
   __shared__ float part[4][D];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+  const int np = pool_rows(pool_len, Tn);
   float4 accp[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) accp[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int t = wave; t < Tn; t += 4) {
+  for (int t = wave; t < np; t += 4) {
     const float* row = y + ((size_t)b * Tn + t) * D;
     float4 x[NI];
     float s = 0.f;
@@ -908,7 +911,7 @@ __global__ void __launch_bounds__(256) tf_pool_kernel(const float* __restrict__ 
   if (wave == 0) {
     float4 x[NI];
     float s = 0.f;
-    const float invT = 1.0f / Tn;
+    const float invT = 1.0f / np;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int c = 4 * (lane + 64 * i);

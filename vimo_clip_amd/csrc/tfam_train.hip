@@ -335,16 +335,16 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
 // ---- head ----------------------------------------------------------------------------------------------------------------
 template <typename T>
 int tr_head_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params& Hd, float* logits, const TrDims& d, const TrWs& ws,
-                float p_mlp, uint64_t seed, hipStream_t s) {
+                float p_mlp, uint64_t seed, const int* pool_len, hipStream_t s) {
   const int D = d.D;
   const TrLayerWs wl = tr_lw(ws, d, d.L - 1);
   const vmc_tfam_layer_params& PL = layers[d.L - 1];
   if (D == 768)
     hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(d.B), dim3(256), 0, s, wl.y3, PL.ln_ffn_g, PL.ln_ffn_b, Hd.cls_ln_g, Hd.cls_ln_b, ws.pool16,
-                       d.T, 1e-5f, ws.pooled32);
+                       d.T, 1e-5f, pool_len, ws.pooled32);
   else
     hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(d.B), dim3(256), 0, s, wl.y3, PL.ln_ffn_g, PL.ln_ffn_b, Hd.cls_ln_g, Hd.cls_ln_b, ws.pool16,
-                       d.T, 1e-5f, ws.pooled32);
+                       d.T, 1e-5f, pool_len, ws.pooled32);
   VMC_CHECK_LAUNCH();
   int rc;
   {
@@ -481,15 +481,17 @@ __device__ __forceinline__ float tr_block_sum(float v, float* red) {      // 256
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
-// H3: blocks 0..B-1: LayerNorm_cls backward of clip b, then the mean-pool's backward dx3[b, t, :] = dpooled[b, :] / T for ALL T rows
-// (AMO_CLIP.py:170 pools padded rows too); block B: the classifier LayerNorm's gamma / beta gradients (sums over the B clips).
+// H3: blocks 0..B-1: LayerNorm_cls backward of clip b, then the mean-pool's backward dx3[b, t, :] = dpooled[b, :] / n on the n pooled
+// rows (n = T without a pool length: AMO_CLIP.py:170 pools padded rows too) and 0 on rows n..T-1 (all T rows are written);
+// block B: the classifier LayerNorm's gamma / beta gradients (sums over the B clips).
 template <int D>
 __global__ void __launch_bounds__(256) tr_head_bwd3_kernel(const float* __restrict__ pooled, const float* __restrict__ dpl, const float* __restrict__ gamma,
                                                            float* __restrict__ dx3, float* __restrict__ g_gamma, float* __restrict__ g_beta, int B,
-                                                           int Tn, float eps) {
+                                                           int Tn, float eps, const int* __restrict__ pool_len) {
   constexpr int NI = D / 256;
   __shared__ float red[4];
   const int tid = threadIdx.x;
+  const int np = pool_rows(pool_len, Tn);
   float ag[NI], ab[NI];
 #pragma unroll
   for (int i = 0; i < NI; ++i) ag[i] = ab[i] = 0.f;
@@ -525,11 +527,11 @@ __global__ void __launch_bounds__(256) tr_head_bwd3_kernel(const float* __restri
     if (params) continue;
     s1 = tr_block_sum(s1, red) * (1.0f / D);
     s2 = tr_block_sum(s2, red) * (1.0f / D);
-    const float invT = 1.0f / Tn;
+    const float invT = 1.0f / np;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const float dp = rstd * (g[i] - s1 - x[i] * s2) * invT;
-      for (int t = 0; t < Tn; ++t) dx3[((size_t)b * Tn + t) * D + tid + 256 * i] = dp;
+      for (int t = 0; t < Tn; ++t) dx3[((size_t)b * Tn + t) * D + tid + 256 * i] = t < np ? dp : 0.f;
     }
   }
   if (params) {
@@ -543,7 +545,7 @@ __global__ void __launch_bounds__(256) tr_head_bwd3_kernel(const float* __restri
 
 template <typename T>
 int tr_head_bwd(const float* dlogits, const vmc_tfam_head_params& Hd, const TrDims& d, const TrWs& ws, float p_mlp, uint64_t seed,
-                hipStream_t s) {
+                const int* pool_len, hipStream_t s) {
   const int D = d.D, Dh = D / 2, B = d.B, C = d.C;
   const TrLayerWs wl = tr_lw(ws, d, d.L - 1);
   const int n1 = Dh / 64 + (C * Dh + C + 511) / 512, n2 = D / 64 + (Dh * D + Dh + 511) / 512;
@@ -562,10 +564,10 @@ int tr_head_bwd(const float* dlogits, const vmc_tfam_head_params& Hd, const TrDi
   VMC_CHECK_LAUNCH();
   if (D == 768)
     hipLaunchKernelGGL((tr_head_bwd3_kernel<768>), dim3(B + 1), dim3(256), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b, B, d.T,
-                       1e-5f);
+                       1e-5f, pool_len);
   else
     hipLaunchKernelGGL((tr_head_bwd3_kernel<512>), dim3(B + 1), dim3(256), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b, B, d.T,
-                       1e-5f);
+                       1e-5f, pool_len);
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -778,6 +780,13 @@ extern "C" size_t vmc_tfam_train_workspace_bytes(int B, int T, int Tk, int D, in
   return tr_ws(nullptr, d).bytes;
 }
 
+extern "C" long long vmc_tfam_train_pool_grad_offset(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross) {
+  TrDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
+  if (tr_check(d)) return -1;
+  const TrWs ws = tr_ws(nullptr, d);
+  return (long long)(uintptr_t)tr_lw(ws, d, L - 1).dx3;      // laid out from a null base: the address is the offset
+}
+
 #define TR_PROLOG()                                                         \
   TrDims d = {B, T, Tk, D, H, ff, L, C, has_cross};                         \
   if (int rc_ = tr_check(d)) return rc_;                                    \
@@ -797,20 +806,34 @@ extern "C" int vmc_tfam_layer_train_fwd(const float* x_in, const float* motion, 
                              : tr_layer_fwd<F16>(x_in, motion, mask, mask_kv, layers, layer, d, ws, p_drop, seeds, s);
 }
 
+extern "C" int vmc_tfam_head_train_fwd_len(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits, void* workspace,
+                                           size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross,
+                                           float p_mlp, uint64_t seed, const int* pool_len, int dtype16, void* stream) {
+  TR_PROLOG();
+  if (!layers || !head || !logits || p_mlp < 0.f || p_mlp >= 1.f) return VMC_E_ARG;
+  return dtype16 == VMC_BF16 ? tr_head_fwd<BF16>(layers, *head, logits, d, ws, p_mlp, seed, pool_len, s)
+                             : tr_head_fwd<F16>(layers, *head, logits, d, ws, p_mlp, seed, pool_len, s);
+}
 extern "C" int vmc_tfam_head_train_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits, void* workspace,
                                        size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, float p_mlp,
                                        uint64_t seed, int dtype16, void* stream) {
-  TR_PROLOG();
-  if (!layers || !head || !logits || p_mlp < 0.f || p_mlp >= 1.f) return VMC_E_ARG;
-  return dtype16 == VMC_BF16 ? tr_head_fwd<BF16>(layers, *head, logits, d, ws, p_mlp, seed, s) : tr_head_fwd<F16>(layers, *head, logits, d, ws, p_mlp, seed, s);
+  return vmc_tfam_head_train_fwd_len(layers, head, logits, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp, seed, nullptr,
+                                     dtype16, stream);
 }
 
+extern "C" int vmc_tfam_head_bwd_len(const float* dlogits, const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
+                                     size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, float p_mlp,
+                                     uint64_t seed, const int* pool_len, int dtype16, void* stream) {
+  TR_PROLOG();
+  if (!dlogits || !layers || !head) return VMC_E_ARG;
+  return dtype16 == VMC_BF16 ? tr_head_bwd<BF16>(dlogits, *head, d, ws, p_mlp, seed, pool_len, s)
+                             : tr_head_bwd<F16>(dlogits, *head, d, ws, p_mlp, seed, pool_len, s);
+}
 extern "C" int vmc_tfam_head_bwd(const float* dlogits, const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
                                  size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, float p_mlp,
                                  uint64_t seed, int dtype16, void* stream) {
-  TR_PROLOG();
-  if (!dlogits || !layers || !head) return VMC_E_ARG;
-  return dtype16 == VMC_BF16 ? tr_head_bwd<BF16>(dlogits, *head, d, ws, p_mlp, seed, s) : tr_head_bwd<F16>(dlogits, *head, d, ws, p_mlp, seed, s);
+  return vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp, seed, nullptr, dtype16,
+                               stream);
 }
 
 extern "C" int vmc_tfam_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, void* workspace,
@@ -822,10 +845,10 @@ extern "C" int vmc_tfam_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, c
                              : tr_layer_bwd<F16>(mask, mask_kv, layers, layer, d, ws, p_drop, seeds, dtype16, s);
 }
 
-extern "C" int vmc_tfam_train_fwd(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
-                                  const vmc_tfam_head_params* head, float* logits, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D,
-                                  int H, int ff, int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, int dtype16,
-                                  void* stream) {
+extern "C" int vmc_tfam_train_fwd_len(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv,
+                                      const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits, void* workspace,
+                                      size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, float p_drop,
+                                      float p_mlp, const uint64_t* seeds, const int* pool_len, int dtype16, void* stream) {
   if (!x || !layers || !head || !logits) return VMC_E_ARG;
   for (int l = 0; l < L; ++l) {
     const int rc = vmc_tfam_layer_train_fwd(l == 0 ? x : nullptr, motion, mask, mask_kv, layers, l, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C,
@@ -833,16 +856,24 @@ extern "C" int vmc_tfam_train_fwd(const float* x, const float* motion, const uin
     if (rc) return rc;
   }
   if (p_mlp > 0.f && !seeds) return VMC_E_ARG;
-  return vmc_tfam_head_train_fwd(layers, head, logits, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp, seeds ? seeds[7 * L] : 0,
-                                 dtype16, stream);
+  return vmc_tfam_head_train_fwd_len(layers, head, logits, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp,
+                                     seeds ? seeds[7 * L] : 0, pool_len, dtype16, stream);
+}
+extern "C" int vmc_tfam_train_fwd(const float* x, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
+                                  const vmc_tfam_head_params* head, float* logits, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D,
+                                  int H, int ff, int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, int dtype16,
+                                  void* stream) {
+  return vmc_tfam_train_fwd_len(x, motion, mask, mask_kv, layers, head, logits, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_drop,
+                                p_mlp, seeds, nullptr, dtype16, stream);
 }
 
-extern "C" int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
-                                  const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff,
-                                  int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, int dtype16, void* stream) {
+extern "C" int vmc_tfam_train_bwd_len(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
+                                      const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H,
+                                      int ff, int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, const int* pool_len,
+                                      int dtype16, void* stream) {
   if (p_mlp > 0.f && !seeds) return VMC_E_ARG;
-  int rc = vmc_tfam_head_bwd(dlogits, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp, seeds ? seeds[7 * L] : 0, dtype16,
-                             stream);
+  int rc = vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp,
+                                 seeds ? seeds[7 * L] : 0, pool_len, dtype16, stream);
   if (rc) return rc;
   TR_PROLOG();
   if (!layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
@@ -862,4 +893,10 @@ extern "C" int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, con
     }
   }
   return 0;
+}
+extern "C" int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
+                                  const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff,
+                                  int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, int dtype16, void* stream) {
+  return vmc_tfam_train_bwd_len(dlogits, mask, mask_kv, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_drop, p_mlp,
+                                seeds, nullptr, dtype16, stream);
 }

@@ -10,6 +10,54 @@ from __future__ import annotations
 import torch
 
 
+def pooled_stream(model):
+    """Which token stream ``model`` (an AMO_CLIP) mean-pools: "rgb" (cross attention, rgb-only), "motion" (flow-only), or None for
+    the two concatenation modes, which cannot be padded further (AMO_CLIP.pools_padded_tokens) and keep exact shapes."""
+    if not getattr(model, "pools_padded_tokens", False):
+        return None
+    return "motion" if model.use_only_flow else "rgb"
+
+
+def pad_to_bucket(rgb, mot, mask_rgb, mask_flow, bucket: int, pooled="rgb"):
+    """Zero-pad a ragged TFAM batch to its length bucket: (rgb, mot, mask_rgb, mask_flow, n).
+
+    RGB and motion tokens [B, T, D] are padded along T, each to its own next multiple of ``bucket``; the masks [B, T] (True / 1 =
+    real token) get zeros on the new rows, and a mask that is None becomes all-true over the ORIGINAL length first -- otherwise
+    the new rows would be attended to.  n is the original length of the ``pooled`` stream ("rgb" | "motion"), to be handed to
+    ``AMO_CLIP.forward(..., pool_len=n)``: the added rows are then masked as keys, feed only their own rows as queries, stay out of
+    the mean-pool and receive a zero gradient, so the padded batch gives the logits and gradients of the unpadded one and every
+    batch whose lengths fall into the same buckets shares one captured graph.  ``bucket <= 1`` or ``pooled is None`` (the
+    concatenation modes): everything is returned as it came, n = None."""
+    if bucket <= 1 or pooled is None:
+        return rgb, mot, mask_rgb, mask_flow, None
+
+    def pad(x, T, fill_mask_like=None):
+        if x is None:
+            x = torch.ones(fill_mask_like.shape[:2], dtype=torch.bool, device=fill_mask_like.device)
+        if x.shape[1] == T:
+            return x
+        return torch.nn.functional.pad(x, (0, 0) * (x.dim() - 2) + (0, T - x.shape[1]))      # zeros behind dim 1
+
+    n = int(mot.shape[1] if pooled == "motion" else rgb.shape[1])
+    Tr, Tf = -(-rgb.shape[1] // bucket) * bucket, -(-mot.shape[1] // bucket) * bucket
+    return pad(rgb, Tr), pad(mot, Tf), pad(mask_rgb, Tr, rgb), pad(mask_flow, Tf, mot), n
+
+
+class _PoolLens:
+    """One-element int32 tensors of the pool lengths seen so far, per device: a replay copies one into the graph's static input, and
+    no step pays a host-to-device transfer for a length it has seen before."""
+
+    def __init__(self):
+        self._t = {}
+
+    def get(self, n, device):
+        key = (int(n), str(device))
+        t = self._t.get(key)
+        if t is None:
+            t = self._t[key] = torch.tensor([int(n)], dtype=torch.int32, device=device)
+        return t
+
+
 class GraphedCallable:
     """Captures ``fn(*static_inputs)`` once; ``__call__(*inputs)`` copies the inputs into the static buffers, replays
     the graph and returns the static outputs (valid until the next call)."""
@@ -53,9 +101,18 @@ class GraphedTrainStep:
     shape), then ``exchange()`` (the bucketed RCCL all-reduce or reduce-scatter + all-gather of parallel.GradientAllReducer, eager:
     collectives are not captured) whose return value (1 / world) goes to the optimiser's device-resident grad_scale, then
     ``opt_fn`` = the fused AdamW + the refresh of the 16-bit copies (one graph, shape independent).  Gradient-ready hooks are
-    silenced while capturing (a replay runs no Python, so the buckets go out after the backward graph, not during it)."""
+    silenced while capturing (a replay runs no Python, so the buckets go out after the backward graph, not during it).
 
-    def __init__(self, step_fn, optimizer, max_graphs: int = 16, exchange=None, opt_fn=None, graph_factory=None):
+    Ragged batches (``bucket > 1``): the first four inputs are taken as (rgb tokens, motion tokens, mask_rgb, mask_flow) and go
+    through ``pad_to_bucket``; ``step_fn`` then receives the padded tensors, the remaining inputs and, last, ``pool_len`` -- a
+    one-element int32 tensor holding the batch's own length, one more static input that is refreshed before every replay and that
+    ``step_fn`` hands to ``AMO_CLIP.forward(pool_len=...)``.  The graph key uses the padded lengths, so one graph serves a whole
+    bucket, exactly (see pad_to_bucket).  ``pooled``: the stream the model pools (``pooled_stream(model)``); None keeps exact
+    shapes, as ``bucket = 1`` does.  Dropout masks are a function of the padded shape (element index ``row * N + col``): a
+    bucketed step draws other masks than an unbucketed one, and the same masks as an eager step on the same padded tensors."""
+
+    def __init__(self, step_fn, optimizer, max_graphs: int = 16, exchange=None, opt_fn=None, graph_factory=None, bucket: int = 1,
+                 pooled="rgb"):
         if getattr(optimizer, "dev_state", None) is None:
             raise ValueError("GraphedTrainStep needs FusedAdam.enable_device_state()")
         if (exchange is None) != (opt_fn is None):
@@ -65,6 +122,8 @@ class GraphedTrainStep:
         self._factory = graph_factory or GraphedCallable
         self._graphs = {}
         self._opt_graph = None
+        self.bucket, self.pooled = int(bucket), pooled
+        self._lens = _PoolLens()
 
     def _live(self):
         o, a = self.opt, self.opt.arena
@@ -90,6 +149,9 @@ class GraphedTrainStep:
 
     def __call__(self, *inputs):
         from . import autograd_ops
+        if self.bucket > 1 and self.pooled is not None:
+            rgb, mot, mr, mf, n = pad_to_bucket(*inputs[:4], self.bucket, self.pooled)
+            inputs = (rgb, mot, mr, mf) + tuple(inputs[4:]) + (self._lens.get(n, rgb.device),)
         key = tuple((tuple(x.shape), x.dtype) if torch.is_tensor(x) else x for x in inputs)
         g = self._graphs.get(key)
         if g is None:

@@ -271,10 +271,25 @@ def set_class_rows(x: torch.Tensor, a, b, F: int, D: int, row_stride: int, dtype
     check(lib.vmc_set_class_rows(ptr(x), ptr(a), ptr(b), F, D, row_stride, dt(x), dt(dtype16), stream()), "set_class_rows")
 
 
-def mean_pool(x: torch.Tensor, B: int, T: int, D: int, dtype16, out16=True, out32=False):
+def pool_len_tensor(pool_len, device):
+    """The logical pool length of include/vmc.h ("POOL LENGTH") as the one-element int32 device tensor the kernels read.
+    None stays None (mean over all rows); an int becomes a new tensor -- do that once, outside any graph capture."""
+    if pool_len is None:
+        return None
+    if torch.is_tensor(pool_len):
+        if pool_len.dtype != torch.int32 or pool_len.numel() != 1 or not pool_len.is_cuda:
+            raise TypeError("pool_len must be an int or a one-element int32 device tensor")
+        return pool_len
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("pool_len given as an int during a graph capture: pass a device tensor (the value would be frozen)")
+    return torch.tensor([int(pool_len)], dtype=torch.int32, device=device)
+
+
+def mean_pool(x: torch.Tensor, B: int, T: int, D: int, dtype16, out16=True, out32=False, pool_len=None):
+    """pool_len (one-element int32 device tensor or None): the mean runs over the first pool_len rows of every clip."""
     o16 = torch.empty((B, D), dtype=dtype16, device=x.device) if out16 else None
     o32 = torch.empty((B, D), dtype=torch.float32, device=x.device) if out32 else None
-    check(lib.vmc_mean_pool(ptr(x), ptr(o16), ptr(o32), B, T, D, dt(x), dt(dtype16), stream()), "mean_pool")
+    check(lib.vmc_mean_pool_len(ptr(x), ptr(o16), ptr(o32), B, T, D, ptr(pool_len), dt(x), dt(dtype16), stream()), "mean_pool")
     return o16, o32
 
 

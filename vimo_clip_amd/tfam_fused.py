@@ -153,15 +153,16 @@ class TfamPack:
             self._pinned.add(key)                      # its address is now part of a graph: never freed while this pack lives
         return ws
 
-    def forward(self, x, motion, mask, mask_kv, has_cross, slot=0):
-        """x [B,T,D] fp32 tokens, motion [B,Tk,D] fp32 (cross mode) or None, masks uint8 [B,T] / [B,Tk] or None."""
+    def forward(self, x, motion, mask, mask_kv, has_cross, slot=0, pool_len=None):
+        """x [B,T,D] fp32 tokens, motion [B,Tk,D] fp32 (cross mode) or None, masks uint8 [B,T] / [B,Tk] or None; pool_len: one-element
+        int32 device tensor, the number of leading rows of every clip that the mean-pool takes (None: all T)."""
         B, T, D = x.shape
         Tk = motion.shape[1] if has_cross else 0
         ws = self.workspace(B, T, Tk, has_cross, slot)
         logits = torch.empty((B, self.C), dtype=torch.float32, device=x.device)
-        check(lib.vmc_tfam_forward(ptr(x), ptr(motion) if has_cross else None, ptr(mask), ptr(mask_kv) if has_cross else None,
-                                   ptr(self.wpack), ptr(self.ppack), ptr(logits), ptr(ws), ws.numel(), B, T, Tk, D, self.H, self.ff,
-                                   self.L, self.C, int(has_cross), dt(self.dtype16), stream()), "tfam_forward")
+        check(lib.vmc_tfam_forward_len(ptr(x), ptr(motion) if has_cross else None, ptr(mask), ptr(mask_kv) if has_cross else None,
+                                       ptr(self.wpack), ptr(self.ppack), ptr(logits), ptr(ws), ws.numel(), B, T, Tk, D, self.H, self.ff,
+                                       self.L, self.C, int(has_cross), ptr(pool_len), dt(self.dtype16), stream()), "tfam_forward")
         return logits
 
 

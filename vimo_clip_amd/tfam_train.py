@@ -89,7 +89,7 @@ class _Tables:
         """(layers array, head struct).  Cached; rebuilt when a parameter, a compute copy or a gradient slot moved.  fresh: a dict
         -> parameters without a gradient slot get new fp32 gradient tensors (collected in it; nothing is cached then)."""
         ps = self.params()
-        key = (ag.weights.generation,
+        key = (ag.weights.generation, tuple(p.requires_grad for p in ps),
                tuple((p._version, p.data_ptr(), 0 if getattr(p, "_vmc_grad", None) is None else p._vmc_grad.data_ptr()) for p in ps))
         if fresh is None:
             if key == self.key:
@@ -182,7 +182,7 @@ class TfamTrainFn(torch.autograd.Function):
     gradients); their values are read through the pointer tables, not through these tensors."""
 
     @staticmethod
-    def forward(ctx, model, x, motion, mask, mask_kv, cross, p_drop, p_mlp, seeds, *params):
+    def forward(ctx, model, x, motion, mask, mask_kv, cross, p_drop, p_mlp, seeds, pool_len, *params):
         dt16 = model.compute_dtype
         B, T, D = x.shape
         Tk = motion.shape[1] if cross else 0
@@ -195,18 +195,23 @@ class TfamTrainFn(torch.autograd.Function):
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         logits = torch.empty((B, dims[7]), dtype=torch.float32, device=x.device)
         sarr = (ctypes.c_uint64 * len(seeds))(*seeds) if seeds else None
-        check(lib.vmc_tfam_train_fwd(ptr(x), ptr(motion) if cross else None, ptr(mask), ptr(mask_kv) if cross else None, layers,
-                                     ctypes.byref(head), ptr(logits), ptr(ws), nbytes, *dims, float(p_drop), float(p_mlp), sarr, dt(dt16),
-                                     stream()), "tfam_train_fwd")
+        check(lib.vmc_tfam_train_fwd_len(ptr(x), ptr(motion) if cross else None, ptr(mask), ptr(mask_kv) if cross else None, layers,
+                                         ctypes.byref(head), ptr(logits), ptr(ws), nbytes, *dims, float(p_drop), float(p_mlp), sarr,
+                                         ptr(pool_len), dt(dt16), stream()), "tfam_train_fwd")
         ctx.model, ctx.tab, ctx.ws, ctx.dims, ctx.cross = model, tab, ws, dims, cross
         ctx.masks, ctx.drop, ctx.sarr, ctx.params = (mask, mask_kv), (float(p_drop), float(p_mlp)), sarr, params
+        ctx.pool_len = pool_len                              # the backward reads the same device value
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
         model, tab, ws, dims, cross = ctx.model, ctx.tab, ctx.ws, ctx.dims, ctx.cross
+        if ws is None:
+            raise RuntimeError("TFAM training chain: backward ran a second time, but the saved activations live in a workspace that "
+                               "the first backward released (retain_graph is not supported on this path)")
         mask, mask_kv = ctx.masks
         p_drop, p_mlp = ctx.drop
+        pool_len = ctx.pool_len
         dt16 = model.compute_dtype
         fresh = {}
         need_fresh = any(p.requires_grad and getattr(p, "_vmc_grad", None) is None for p in ctx.params)
@@ -222,11 +227,12 @@ class TfamTrainFn(torch.autograd.Function):
         if not ag.grad_ready_hooks and done is None:
             # nobody waits for a layer's gradients (single process): the whole backward in one call -- the dgrad chains of all layers,
             # then every weight gradient in ONE grouped launch (vmc_tfam_train_bwd)
-            check(lib.vmc_tfam_train_bwd(ptr(dlogits), ptr(mask), ptr(mask_kv) if cross else None, layers, ctypes.byref(head), ptr(ws), nbytes,
-                                         *dims, p_drop, p_mlp, sarr, dt(dt16), stream()), "tfam_train_bwd")
+            check(lib.vmc_tfam_train_bwd_len(ptr(dlogits), ptr(mask), ptr(mask_kv) if cross else None, layers, ctypes.byref(head), ptr(ws),
+                                             nbytes, *dims, p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_bwd")
         else:
-            check(lib.vmc_tfam_head_bwd(ptr(dlogits), layers, ctypes.byref(head), ptr(ws), nbytes, *dims, p_mlp,
-                                        int(sarr[SEEDS_PER_LAYER * L]) if sarr is not None else 0, dt(dt16), stream()), "tfam_head_bwd")
+            check(lib.vmc_tfam_head_bwd_len(ptr(dlogits), layers, ctypes.byref(head), ptr(ws), nbytes, *dims, p_mlp,
+                                            int(sarr[SEEDS_PER_LAYER * L]) if sarr is not None else 0, ptr(pool_len), dt(dt16), stream()),
+                  "tfam_head_bwd")
             _report(head_params)
             if done is not None:                                 # group L = the classifier
                 done(L)
@@ -245,7 +251,7 @@ class TfamTrainFn(torch.autograd.Function):
                     done(l)
         grads = tuple((fresh.get(id(p)) if p.requires_grad and getattr(p, "_vmc_grad", None) is None else None) for p in ctx.params)
         ctx.ws = None
-        return (None,) * 9 + grads
+        return (None,) * 10 + grads
 
 
 def _report(params):
@@ -256,8 +262,10 @@ def _report(params):
                     hook(p)
 
 
-def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn):
-    """Train-mode forward of ``model`` through the fused chain (autograd-tracked); None when the shapes are outside its set."""
+def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None):
+    """Train-mode forward of ``model`` through the fused chain (autograd-tracked); None when the shapes are outside its set.
+    pool_len: one-element int32 device tensor, the rows of every clip that the mean-pool takes (None: all T); the backward
+    leaves a zero gradient on the other rows."""
     B, T, _ = x.shape
     Tk = motion.shape[1] if cross else 0
     if x.requires_grad or (cross and motion.requires_grad) or not supported(model, B, T, Tk, cross):
@@ -281,4 +289,4 @@ def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn):
             seeds += row
         seeds.append(seed_fn() if p_mlp > 0.0 else 0)
     tab = _tables(model, model.compute_dtype, cross)
-    return TfamTrainFn.apply(model, x, motion, mask, mask_kv, cross, p, p_mlp, tuple(seeds), *tab.params())
+    return TfamTrainFn.apply(model, x, motion, mask, mask_kv, cross, p, p_mlp, tuple(seeds), pool_len, *tab.params())
