@@ -528,6 +528,7 @@ int vmc_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
  * the dropout seeds must not be host scalars frozen into the graph -- ADVICE r1).
  *   state  u64 [2 + n_seeds] in device memory: [0] step count t (start at 0), [1] base seed, [2..] this step's dropout seeds
  *   hyper  f32 [4], 16-byte aligned: {lr, lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), grad_scale}; the host writes [0] and [3]
+ *          (with gradient clipping vmc_grad_clip_dev writes [3], below)
  * vmc_train_tick: t += 1, recomputes hyper[1..2] and the n_seeds seeds (splitmix of base seed, t and the index); enqueue it once
  * per step before the forward.  vmc_adam_step_dev = vmc_adam_step reading its four scalars from `hyper`.
  * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd): a value < 2^63 is the seed itself; with bit
@@ -556,6 +557,21 @@ int vmc_adam_step_dev_bg(float* p, const float* g, float* m, float* v, size_t n,
 int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
                         float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1, float beta2,
                         float eps, float weight_decay, int decoupled_wd, int dtype16, void* stream);
+/* Gradient clipping computed on the device (torch.nn.utils.clip_grad_norm_, train.py:105-106, inside a captured step): the global
+ * norm of `grad` (n floats, 16-byte aligned) and from it the factor the Adam kernels read from hyper[3].  Enqueue it after the
+ * backward (and, under data parallelism, after the gradient exchange) and before vmc_adam_step_dev / vmc_adam_cast_multi.
+ *   clip  f32 [4] in device memory, 16-byte aligned:
+ *     [0] base_scale  host-written   what hyper[3] holds without clipping: 1, or 1 / world when `grad` is a sum over ranks
+ *     [1] max_norm    host-written   the clipping threshold
+ *     [2] norm        device-written ||grad||_2 * |base_scale|: the norm of the AVERAGED gradient
+ *     [3] coef        device-written min(1, max_norm / (norm + 1e-6)), torch's coefficient
+ *   and hyper[3] = base_scale * coef (device-written: with clipping the host leaves hyper[3] alone and writes clip[0]).
+ * Non-finite gradients propagate as in torch (an infinite norm gives coef 0, a NaN norm a NaN coef); nothing is skipped.
+ * Two launches, no atomics: workgroup partials (doubles, one per workgroup, in `workspace`: vmc_grad_clip_workspace_bytes(n),
+ * 16-byte aligned) are added in a fixed order, so the same gradient gives the same bits on every call and every replay. */
+size_t vmc_grad_clip_workspace_bytes(size_t n);
+int vmc_grad_clip_dev(const float* grad, size_t n, float* hyper, float* clip, void* workspace, size_t workspace_bytes,
+                      void* stream);
 /* sum of squares of a flat f32 buffer, accumulated (+=) into out[0] (global grad norm). */
 int vmc_sumsq(const float* x, size_t n, float* out, void* stream);
 

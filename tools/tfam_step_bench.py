@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """TFAM train step at batch B (configs[3] geometry, dropout 0.1 / 0.1): eager and as ONE hipGraph replay, with and without the
-backward-overlapped AdamW.    python tools/tfam_step_bench.py [B] [iters]"""
+backward-overlapped AdamW.    python tools/tfam_step_bench.py [B] [iters] [max_grad_norm]
+max_grad_norm: clip on the device inside the step (optim.FusedAdam.step(max_grad_norm=...)); omitted = no clipping."""
 import os
 import sys
 import time
@@ -16,6 +17,7 @@ from vimo_clip_amd.TFAM.models import AMO_CLIP  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+clip = float(sys.argv[3]) if len(sys.argv) > 3 else None
 dev = torch.device("cuda", 0)
 
 
@@ -50,7 +52,7 @@ for overlap in (False,):
             out = m(rgb, mot, mask_rgb=mk, mask_flow=mk)
             loss, dl = loss_and_grad(bce_with_logits_loss, out, y)
             out.backward(dl)
-            opt.step()
+            opt.step(max_grad_norm=clip)
             return loss, out.detach()
 
         te = timeit(lambda: dev_step(rgb, mot, mk, y), max(20, iters // 4))
@@ -58,4 +60,4 @@ for overlap in (False,):
         tg = timeit(lambda: g(rgb, mot, mk, y), iters)
         gr = next(iter(g._graphs.values()))
         tr = timeit(lambda: gr.replay(), iters)
-        print(f"B={B} fused={fused} overlap={overlap}: eager {te*1e6:8.1f} us   captured {tg*1e6:8.1f} us   bare replay {tr*1e6:8.1f} us", flush=True)
+        print(f"B={B} fused={fused} overlap={overlap} clip={clip}: eager {te*1e6:8.1f} us   captured {tg*1e6:8.1f} us   bare replay {tr*1e6:8.1f} us", flush=True)

@@ -37,6 +37,7 @@ class Config:
         self.dropout, self.mlp_dropout, self.device, self.checkpoint_dir, self.log_dir = 0.1, 0.1, "cuda", "checkpoints", "logs"
         self.task, self.motion_key, self.use_graphs = "multilabel", "flow", False    # use_graphs: hipGraph replay of the eval forward
         self.graph_bucket = 1      # use_graphs with ragged loaders: pad clip lengths to multiples of this, one graph per bucket (graphs.pad_to_bucket)
+        self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
 
@@ -64,6 +65,8 @@ class Config:
             kw["motion_key"] = "frame_diff"
         if "graph_bucket" in t:                     # not a key of the reference's YAML: optional
             kw["graph_bucket"] = int(t["graph_bucket"])
+        if t.get("grad_clip_norm") is not None:     # optional as well
+            kw["grad_clip_norm"] = float(t["grad_clip_norm"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -210,6 +213,7 @@ class ModelTrainer:
         self.optimizer = FusedAdam(self.arena, lr=1e-4, weight_decay=0.1, decoupled=True)       # lr hard-coded as :53
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=config.epochs, eta_min=1e-6)
         self.reducer = parallel.GradientAllReducer(self.arena.flat_grad).attach(self.arena)   # buckets go out during the backward
+        self.grad_clip_norm = getattr(config, "grad_clip_norm", None)
         bucket = int(getattr(config, "graph_bucket", 1))
         self._graphed_eval = GraphedEvalForward(model, config, bucket=bucket) if getattr(config, "use_graphs", False) else None
         self._graphed_train = None
@@ -224,7 +228,7 @@ class ModelTrainer:
                 self._graphed_train = GraphedTrainStep(self._device_state_step, self.optimizer, **ragged)
             else:
                 self._graphed_train = GraphedTrainStep(self._device_state_fwd_bwd, self.optimizer, exchange=self.reducer.all_reduce,
-                                                       opt_fn=self.optimizer.step, **ragged)
+                                                       opt_fn=self._device_state_update, **ragged)
         if world == 1 and os.environ.get("VMC_ADAM_OVERLAP", "0") == "1":
             # AdamW of a finished layer on a side stream beside the backward of the layers below it.  Bit-identical, but measured
             # SLOWER on MI355X (captured B = 8 step 0.88 -> 0.95-1.01 ms: the fork / join edges of a multi-stream hipGraph cost more
@@ -243,8 +247,13 @@ class ModelTrainer:
         output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)      # criterion(output, labels); loss.backward() (:81-83)
         output.backward(dlogits)
-        self.optimizer.step()
+        self._device_state_update()
         return loss, output.detach()
+
+    def _device_state_update(self):
+        """[clip on the device +] AdamW: the tail of the one-graph step, and the data-parallel step's optimiser graph (the arena
+        then holds the rank sum, and grad_scale = 1 / world is already in device memory: GraphedTrainStep)."""
+        self.optimizer.step(max_grad_norm=self.grad_clip_norm)
 
     def _device_state_fwd_bwd(self, rgb, mot, mr, mf, labels, pool_len=None):
         """The data-parallel step's first graph: tick + forward + loss + backward (the exchange and AdamW follow outside it)."""
@@ -274,7 +283,7 @@ class ModelTrainer:
                 output, labels = self._forward(batch)
                 loss = self.criterion(output, labels)
                 loss.backward()
-                self.optimizer.step(grad_scale=self.reducer.all_reduce())
+                self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
             total += loss.detach()
             n += 1
             self.mAP_metric.update(output, labels.to(dtype=torch.int))

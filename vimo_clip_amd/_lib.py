@@ -103,6 +103,8 @@ SIGNATURES = {
     "vmc_adam_step_dev": (I, [P, P, P, P, Z, P, F, F, F, F, I, P]),
     "vmc_adam_step_dev_bg": (I, [P, P, P, P, Z, P, F, F, F, F, I, I, P]),
     "vmc_adam_cast_multi": (I, [P, I, I, P, I, I, P, P, P, P, P, F, F, F, F, I, I, P]),
+    "vmc_grad_clip_workspace_bytes": (Z, [Z]),
+    "vmc_grad_clip_dev": (I, [P, Z, P, P, P, Z, P]),
     "vmc_sumsq": (I, [P, Z, P, P]),
 }
 

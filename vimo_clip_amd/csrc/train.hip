@@ -272,6 +272,82 @@ extern "C" int vmc_adam_step_dev_bg(float* p, const float* g, float* m, float* v
   return 0;
 }
 
+// ---- gradient clipping on the device (clip_grad_norm_ inside a captured step, train.py:105-106) -----------------------
+// Store and sum: every workgroup of pass one leaves the sum of squares of its grid-stride share in part[blockIdx.x]; pass two (one
+// workgroup) adds the partials in a fixed order and writes clip[2..3] and hyper[3] (include/vmc.h).  No atomics: the result does not
+// depend on the order in which workgroups finish, so a replayed step repeats bit for bit.  A thread squares and adds in fp32 (at
+// most a few dozen terms per accumulator even for a 33 M-element arena); everything that is summed across threads is a double.
+#define CLIP_BLOCKS 2048      // 256 CUs x 8 workgroups of 256 threads
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ inline double block_sum_f64(double a, double* sm) {      // 256 threads, sm = 4 doubles of LDS, one call per kernel
+  a = wave_sum_f64(a);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
+  __syncthreads();
+  return (sm[0] + sm[1]) + (sm[2] + sm[3]);
+}
+
+__global__ void __launch_bounds__(256) grad_sumsq_partial_kernel(const float* __restrict__ g, size_t n, double* __restrict__ part) {
+  __shared__ double sm[4];
+  const size_t n4 = n >> 2;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  float4 acc[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+  // two float4 in flight per thread, as adam_kernel reads them
+  for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
+    const size_t i1 = i0 + stride;
+    const float4 a = ((const float4*)g)[i0];
+    const float4 b = i1 < n4 ? ((const float4*)g)[i1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    acc[0].x += a.x * a.x; acc[0].y += a.y * a.y; acc[0].z += a.z * a.z; acc[0].w += a.w * a.w;
+    acc[1].x += b.x * b.x; acc[1].y += b.y * b.y; acc[1].z += b.z * b.z; acc[1].w += b.w * b.w;
+  }
+  double s = (((double)acc[0].x + (double)acc[0].y) + ((double)acc[0].z + (double)acc[0].w)) +
+             (((double)acc[1].x + (double)acc[1].y) + ((double)acc[1].z + (double)acc[1].w));
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const float t = g[(n4 << 2) + threadIdx.x];
+    s += (double)(t * t);
+  }
+  s = block_sum_f64(s, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(256) grad_clip_finish_kernel(const double* __restrict__ part, int n_part, float* __restrict__ hyper,
+                                                               float* __restrict__ clip) {
+  __shared__ double sm[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n_part; i += 256) s += part[i];
+  s = block_sum_f64(s, sm);
+  if (threadIdx.x == 0) {
+    const float base = clip[0], max_norm = clip[1];
+    const double norm = sqrt(s) * fabs((double)base);                  // of the AVERAGED gradient (optim.clipped_grad_scale)
+    const double c = (double)max_norm / (norm + 1e-6);
+    const float coef = (float)(c < 1.0 ? c : (c != c ? c : 1.0));      // torch.clamp(max=1.0): a NaN norm gives a NaN coefficient
+    clip[2] = (float)norm;
+    clip[3] = coef;
+    hyper[3] = base * coef;
+  }
+}
+
+static inline int grad_clip_blocks(size_t n) { return grid_for(n >> 2, 512, CLIP_BLOCKS); }      // 512 float4 per workgroup and trip
+
+extern "C" size_t vmc_grad_clip_workspace_bytes(size_t n) { return (size_t)grad_clip_blocks(n) * sizeof(double); }
+
+extern "C" int vmc_grad_clip_dev(const float* grad, size_t n, float* hyper, float* clip, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+  if (!grad || !hyper || !clip || !workspace || n == 0) return VMC_E_ARG;
+  if (workspace_bytes < vmc_grad_clip_workspace_bytes(n)) return VMC_E_ARG;
+  if (((uintptr_t)grad | (uintptr_t)hyper | (uintptr_t)clip | (uintptr_t)workspace) & 15) return VMC_E_ALIGN;
+  hipStream_t s = (hipStream_t)stream;
+  const int blocks = grad_clip_blocks(n);
+  hipLaunchKernelGGL(grad_sumsq_partial_kernel, dim3(blocks), dim3(256), 0, s, grad, n, (double*)workspace);
+  VMC_CHECK_LAUNCH();
+  hipLaunchKernelGGL(grad_clip_finish_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, blocks, hyper, clip);
+  VMC_CHECK_LAUNCH();
+  return 0;
+}
+
 // ---- sum of squares (global grad-norm for clip_grad_norm_, train.py:105-106) ----------------------
 __global__ void __launch_bounds__(256) sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
   __shared__ float sm[4];

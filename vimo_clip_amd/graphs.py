@@ -100,7 +100,8 @@ class GraphedTrainStep:
     TWO graphs with the gradient exchange between them -- ``step_fn`` = tick + forward + loss + backward (one graph per batch
     shape), then ``exchange()`` (the bucketed RCCL all-reduce or reduce-scatter + all-gather of parallel.GradientAllReducer, eager:
     collectives are not captured) whose return value (1 / world) goes to the optimiser's device-resident grad_scale, then
-    ``opt_fn`` = the fused AdamW + the refresh of the 16-bit copies (one graph, shape independent).  Gradient-ready hooks are
+    ``opt_fn`` = [vmc_grad_clip_dev over the rank-summed arena when it passes ``max_grad_norm``, base_scale = 1 / world +] the fused
+    AdamW + the refresh of the 16-bit copies (one graph, shape independent).  Gradient-ready hooks are
     silenced while capturing (a replay runs no Python, so the buckets go out after the backward graph, not during it).
 
     Ragged batches (``bucket > 1``): the first four inputs are taken as (rgb tokens, motion tokens, mask_rgb, mask_flow) and go
@@ -127,14 +128,16 @@ class GraphedTrainStep:
 
     def _live(self):
         o, a = self.opt, self.opt.arena
-        return (a.flat_param, a.flat_grad, o.m, o.v, o.dev_state, o.dev_hyper)
+        live = (a.flat_param, a.flat_grad, o.m, o.v, o.dev_state, o.dev_hyper)
+        clip = getattr(o, "dev_clip", None)            # device-side gradient clipping in use: its norm / coefficient slots too
+        return live if clip is None else live + (clip,)
 
     def _capture(self, fn, inputs):
         from . import autograd_ops
         o = self.opt
         live = self._live()
         saved = [t.clone() for t in live]
-        count = o.step_count
+        count, host = o.step_count, getattr(o, "_hyper_host", None)
         hooks = list(autograd_ops.grad_ready_hooks)
         autograd_ops.grad_ready_hooks[:] = []          # no collective inside a warm-up or a capture
         try:
@@ -144,6 +147,10 @@ class GraphedTrainStep:
         for t, s in zip(live, saved):
             t.copy_(s)
         o.step_count = count
+        now = getattr(o, "_hyper_host", None)
+        if now is not None and now != host:        # the warm-up moved a host-written slot (first clipped step, another max_grad_norm): kept, so written again
+            o._hyper_host = None
+            o.sync_hyper(now[1])
         autograd_ops.weights.refresh()          # the 16-bit compute copies follow the restored masters
         return g
 

@@ -90,22 +90,62 @@ class FusedAdam:
     def enable_device_state(self, base_seed: int = 0x5EED):
         """Move the step count / bias corrections / learning rate / dropout seeds into device memory (vmc_train_tick,
         vmc_adam_step_dev): ``tick()`` + ``step()`` then enqueue only launches whose arguments never change, so a captured
-        step replays correctly.  ``sync_hyper()`` must be called (outside a capture) whenever lr or grad_scale change."""
+        step replays correctly.  ``sync_hyper()`` must be called (outside a capture) whenever lr or grad_scale change.
+        ``step(max_grad_norm=x)`` clips on the device (vmc_grad_clip_dev, ``_set_clip``)."""
         dev = self.arena.flat_param.device
         self.dev_state = torch.zeros(2 + self.N_SEEDS, dtype=torch.int64, device=dev)
         self.dev_state[0] = self.step_count
         self.dev_state[1] = int(base_seed) & 0x7FFFFFFFFFFFFFFF
         self.dev_hyper = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.dev_clip = self._clip_ws = self._clip_max = None
         self._hyper_host = None
         self.sync_hyper()
         return self
 
     def sync_hyper(self, grad_scale: float = 1.0):
-        want = (float(self.param_groups[0]["lr"]), float(grad_scale))
+        """lr and grad_scale (1, or 1 / world over a rank-summed arena) -> device memory, only when one of them changed.  While
+        clipping is on, hyper[3] belongs to vmc_grad_clip_dev: grad_scale goes to dev_clip[0] (base_scale) beside the threshold."""
+        want = (float(self.param_groups[0]["lr"]), float(grad_scale), self._clip_max)
         if self._hyper_host != want:
             self.dev_hyper[0] = want[0]
-            self.dev_hyper[3] = want[1]
+            if self._clip_max is None:
+                self.dev_hyper[3] = want[1]
+            else:
+                self.dev_clip[0] = want[1]
+                self.dev_clip[1] = want[2]
             self._hyper_host = want
+
+    def _set_clip(self, max_grad_norm):
+        """Device-state mode: turn clipping on (first use allocates ``dev_clip`` = {base_scale, max_norm, norm, coef} and the
+        reduction workspace), change the threshold, or turn it off (the host owns hyper[3] again).  All of these write device
+        memory from the host, which a capture would not record: inside one they raise, as a changed ``_fused_plan`` does."""
+        want = None if max_grad_norm is None else float(max_grad_norm)
+        if want == self._clip_max:
+            return
+        if self.dev_hyper.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("max_grad_norm changed while a graph is being captured: run one eager step with it first")
+        if want is not None and self.dev_clip is None:
+            dev, n = self.arena.flat_param.device, self.arena.numel
+            self.dev_clip = torch.zeros(4, dtype=torch.float32, device=dev)
+            self._clip_ws = torch.empty(int(lib.vmc_grad_clip_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        grad_scale = self._hyper_host[1] if self._hyper_host is not None else 1.0
+        self._clip_max, self._hyper_host = want, None
+        self.sync_hyper(grad_scale)
+
+    @property
+    def last_grad_norm(self):
+        """One-element device view: the norm of the (averaged) gradient the last clipped step saw.  No synchronisation."""
+        return self._clip_view(2)
+
+    @property
+    def last_clip_coef(self):
+        """One-element device view: the last clipped step's coefficient min(1, max_norm / (norm + 1e-6))."""
+        return self._clip_view(3)
+
+    def _clip_view(self, i):
+        if getattr(self, "dev_clip", None) is None:
+            raise RuntimeError("no device-side clipping yet: enable_device_state() and step(max_grad_norm=...) come first")
+        return self.dev_clip[i:i + 1]
 
     def tick(self):
         """Start of a step in device-state mode: t += 1, bias corrections and this step's dropout seeds (one launch)."""
@@ -203,8 +243,10 @@ class FusedAdam:
         a = self.arena
         dev_mode = getattr(self, "dev_state", None) is not None
         ov = getattr(self, "_ov", None)
-        if dev_mode and max_grad_norm is not None:
-            raise ValueError("gradient clipping needs a host read of the norm: not available in device-state mode")
+        if dev_mode:
+            if max_grad_norm is not None and ov is not None:
+                raise ValueError("backward-overlapped optimiser steps cannot be combined with grad_scale / max_grad_norm")
+            self._set_clip(max_grad_norm)
         if ov is not None and ov["used"]:
             # some ranges were updated during the backward: finish the others on this stream, then join
             if max_grad_norm is not None or grad_scale != 1.0:
@@ -223,7 +265,10 @@ class FusedAdam:
             ov["used"] = False
             self._step_open = False
             return
-        if max_grad_norm is not None:              # torch.nn.utils.clip_grad_norm_ (train.py:105-106)
+        if max_grad_norm is not None and dev_mode:  # the same, computed on the device: hyper[3] = base_scale * coefficient
+            check(lib.vmc_grad_clip_dev(ptr(a.flat_grad), a.numel, ptr(self.dev_hyper), ptr(self.dev_clip), ptr(self._clip_ws),
+                                        self._clip_ws.numel(), stream()), "grad_clip_dev")
+        elif max_grad_norm is not None:            # torch.nn.utils.clip_grad_norm_ (train.py:105-106)
             grad_scale = clipped_grad_scale(float(a.grad_norm().item()), grad_scale, max_grad_norm)
         self._open_step()
         if dev_mode and self._fused_update():          # AdamW + refresh of the 16-bit copies in one pass over the masters
