@@ -364,8 +364,8 @@ int vmc_cross_entropy_loss(const float* logits, const long long* target_index, c
                            float* dlogits, int rows, int C, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * K11-K14 fused — the TFAM forward as a chain of weight-streaming launches for short clips (T, Tk <= 32,
- * d_model 512 / 768, head_dim 64 / 96): AttentionLayer.forward (TFAM/models/AMO_CLIP.py:37-51) in 6 launches
+ * K11-K14 fused — the TFAM forward as a chain of weight-streaming launches for short clips (T, Tk <= 64,
+ * d_model 512 / 768, head_dim 64 / 96; vmc_tfam_supported): AttentionLayer.forward (TFAM/models/AMO_CLIP.py:37-51) in 6 launches
  * with the LayerNorms, both attentions, bias / ReLU / residual adds and casts in prologues and epilogues;
  * the K|V projections of ALL layers' cross attention hoisted into one GEMM over the raw motion tokens
  * (:43-45 projects the same tokens in every layer); mean-pool over all T rows + classifier (:84,:170).
@@ -399,6 +399,10 @@ int vmc_tfam_fold_layernorm(const float* W, const float* bias, const float* gamm
                             float* bias_out, int rows, int cols, int dtype16, void* stream);
 /* Scratch for one forward of B clips (activations of one layer at a time + the hoisted K|V); caller-owned. */
 size_t vmc_tfam_workspace_bytes(int B, int T, int Tk, int D, int ff, int L, int C, int has_cross);
+/* Host only (no device is touched): 0 when the fused chain takes these shapes -- train = 0: the eval forward below; train = 1: the
+ * training chains further down -- else the error code that every entry of that chain returns for them, before any launch.  A caller
+ * that has another path for unsupported shapes asks here first. */
+int vmc_tfam_supported(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int train);
 /* Hoisted cross-attention K|V: ws.kv[B*Tk, L*2D] = motion[B*Tk, D] (fp32) x kv_all^T + bias  (AMO_CLIP.py:43-45, all layers). */
 int vmc_tfam_kv_fwd(const float* motion, const void* wpack, const float* ppack, void* workspace, size_t workspace_bytes,
                     int B, int T, int Tk, int D, int H, int ff, int L, int C, int dtype16, void* stream);

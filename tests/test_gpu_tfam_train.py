@@ -188,6 +188,19 @@ def test_unsupported_shapes_take_the_per_op_path(monkeypatch):
     assert calls in ([], [False]) and np.isfinite(loss) and grads       # declined by AMO_CLIP._fused_inputs or by forward_train
 
 
+def test_class_counts_the_head_backward_cannot_hold_take_the_per_op_path(monkeypatch):
+    """484 classes: 32 rows of dlogits do not fit the LDS of the head backward's first kernel.  The training chain declines the
+    batch up front (vmc_tfam_supported) instead of failing in backward() after its forward has run."""
+    from vimo_clip_amd import tfam_train
+    calls = _count_fused(monkeypatch)
+    c = dict(name="c484", D=512, H=8, L=1, ff=512, C=484, B=2, Tr=16, Tf=16, mode="cross", pe=False, ragged=False, seed=61)
+    m = _model(c, dropout=0.1, mlp_dropout=0.1)
+    assert not tfam_train.supported(m, 2, 16, 16, True) and tfam_train.supported(_model(dict(c, C=480)), 2, 16, 16, True)
+    loss, _, grads = _step(m, c, True)
+    assert calls in ([], [False]), "the fused training chain was not declined"      # by AMO_CLIP._fused_inputs or by forward_train
+    assert np.isfinite(loss) and grads and all(torch.isfinite(g).all() for g in grads.values())
+
+
 @pytest.mark.parametrize("device_state", [False, True], ids=["host-scalars", "device-state"])
 def test_backward_overlapped_adamw_equals_the_plain_step(device_state):
     """FusedAdam.enable_backward_overlap: AdamW (+ the 16-bit copy refresh) of a layer whose gradients are complete runs on a side

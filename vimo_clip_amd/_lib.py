@@ -80,6 +80,7 @@ SIGNATURES = {
     "vmc_tfam_pack_offset": (ctypes.c_longlong, [I, I, I, I, I, I]),
     "vmc_tfam_fold_layernorm": (I, [P, P, P, P, P, P, I, I, I, P]),
     "vmc_tfam_workspace_bytes": (Z, [I, I, I, I, I, I, I, I]),
+    "vmc_tfam_supported": (I, [I] * 10),
     "vmc_tfam_kv_fwd": (I, [P, P, P, P, Z, I, I, I, I, I, I, I, I, I, P]),
     "vmc_tfam_layer_fwd": (I, [P, P, P, P, P, I, P, Z, I, I, I, I, I, I, I, I, I, I, P]),
     "vmc_tfam_head_fwd": (I, [P, P, P, P, Z, I, I, I, I, I, I, I, I, I, I, P]),

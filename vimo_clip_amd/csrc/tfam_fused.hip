@@ -27,8 +27,8 @@
 // summed through LDS.  MFMA operands are passed as (W, X) so a lane owns 4 consecutive output columns of one row.
 // Workgroups that share a W tile are given block ids that agree mod 8 (same XCD, same L2).
 //
-// Supported: T, Tk <= 32, d_model in {512, 768}, head_dim in {64, 96}, (clips per block) * nhead a multiple of 4.
-// Everything else returns VMC_E_SHAPE and the caller uses the general per-op path.
+// Supported: tfam_check of tfam_route.h (T, Tk <= 64, d_model in {512, 768}, head_dim in {64, 96}, ...), which also plans every launch
+// below.  Everything else returns VMC_E_SHAPE before the first launch and the caller uses the general per-op path.
 #include "tfam_kernels.h"
 
 // ---- pack layout ---------------------------------------------------------------------------------------------------------
@@ -72,69 +72,20 @@ extern "C" long long vmc_tfam_pack_offset(int slot, int layer, int D, int ff, in
   }
 }
 
-// workspace: [y f32 M*D][xa f32 M*D][xb f32 M*D][qkv16 M*3D][q16 M*D][h16 M*ff][kv16 Mk*L*2D][pool16 B*D][g16 B*D/2]
-//            [q frag][self-k frag][cross-k frag x L]   (fragment-major, tf_frag_off; the row-major q / k columns stay unused)
 namespace {
-struct TfWs {
-  float *y, *xa, *xb;
-  uint16_t *qkv, *q, *h, *kv, *pool, *g;
-  uint16_t *qf, *kf, *kxf;      // fragment-major q, self k, and (per layer) cross k
-  size_t kxf_stride;            // elements between two layers' cross-k buffers
-  size_t bytes;
-};
-inline TfWs tf_ws(void* base, const TfDims& d) {
-  const size_t M = (size_t)d.B * d.T, Mk = (size_t)d.B * (d.has_cross ? d.Tk : 0);
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  char* p = (char*)base;
-  TfWs w;
-  size_t o = 0;
-  w.y = (float*)(p + o); o += al(M * d.D * 4);
-  w.xa = (float*)(p + o); o += al(M * d.D * 4);
-  w.xb = (float*)(p + o); o += al(M * d.D * 4);
-  w.qkv = (uint16_t*)(p + o); o += al(M * 3 * d.D * 2);
-  w.q = (uint16_t*)(p + o); o += al(M * d.D * 2);
-  w.h = (uint16_t*)(p + o); o += al(M * d.ff * 2);
-  w.kv = (uint16_t*)(p + o); o += al(Mk * d.L * 2 * d.D * 2);
-  w.pool = (uint16_t*)(p + o); o += al((size_t)d.B * d.D * 2);
-  w.g = (uint16_t*)(p + o); o += al((size_t)d.B * (d.D / 2) * 2);
-  const int H = d.H > 0 ? d.H : 8, dh = d.D / H;
-  const size_t fe = tf_frag_elems(d.B, H, dh, tf_ntt(d.T > d.Tk ? d.T : d.Tk));
-  w.qf = (uint16_t*)(p + o); o += al(fe * 2);
-  w.kf = (uint16_t*)(p + o); o += al(fe * 2);
-  w.kxf = (uint16_t*)(p + o); w.kxf_stride = al(fe * 2) / 2; o += (d.has_cross ? d.L : 0) * al(fe * 2);
-  w.bytes = o;
-  return w;
-}
-
-template <typename T, int PRO, int EPI>
-int tf_gemm_k(TfArgs& a, int bn, hipStream_t s) {
-  switch (a.K) {
-    case 768: return tf_dispatch_bn<T, PRO, EPI, 768>(a, bn, s);
-    case 512: return tf_dispatch_bn<T, PRO, EPI, 512>(a, bn, s);
-    case 384: if constexpr (PRO == PRO_16) return tf_dispatch_bn<T, PRO, EPI, 384>(a, bn, s); else return VMC_E_SHAPE;
-    case 256: if constexpr (PRO == PRO_16) return tf_dispatch_bn<T, PRO, EPI, 256>(a, bn, s); else return VMC_E_SHAPE;
-    default: return VMC_E_SHAPE;
-  }
-}
+const TfamOverrides kNoOverrides;      // the A/B switches are the training chain's
 
 inline TfArgs tf_kv_layer_args(const float* motion, const uint16_t* wp, const float* pp, int layer, const TfDims& d, const TfWs& w);
 
 // stand-alone K|V projection of every layer (vmc_tfam_kv_fwd; vmc_tfam_forward pairs each layer's with its qkv launch instead)
 template <typename T>
 int tf_kv_impl(const float* motion, const uint16_t* wp, const float* pp, const TfDims& d, const TfWs& w, hipStream_t s) {
+  const TfamPlan plan = tfam_route_kv(d, tfam_blocks(d), kNoOverrides);
   for (int l = 0; l < d.L; ++l) {
     TfArgs a = tf_kv_layer_args(motion, wp, pp, l, d, w);
-    if (int rc = tf_gemm_k<T, PRO_F32, EPI_ACT16>(a, tf_pick_bn(a.M, a.N, a.rpb, a.K, false), s)) return rc;
+    if (int rc = tf_run_single<T, PRO_F32, EPI_ACT16, false>(a, plan, s)) return rc;
   }
   return 0;
-}
-
-// a layer's qkv projection and its cross-attention K|V projection in ONE launch
-template <typename T, int PRO>
-int tf_qkv_kv_pair(TfArgs& a, TfArgs& b, int bn, hipStream_t s) {
-#define TF_PAIR(BNV) (a.K == 768 ? tf_launch_pair<T, BNV, PRO, EPI_ACT16, 768>(a, b, s) : tf_launch_pair<T, BNV, PRO, EPI_ACT16, 512>(a, b, s))
-  TF_BN_SWITCH(bn, TF_PAIR)
-#undef TF_PAIR
 }
 
 // K|V of ONE layer (rows layer*2D.. of kv_all), written into that layer's columns of ws.kv
@@ -150,28 +101,15 @@ inline TfArgs tf_kv_layer_args(const float* motion, const uint16_t* wp, const fl
   return a;
 }
 
-// column tile of a paired launch: the widest that keeps both problems inside one resident round (1 workgroup per CU)
-inline int tf_pick_bn_pair(int Ma, int Na, int rpba, int Mb, int Nb, int K) {
-  const int cands[4] = {16, 32, 48, 64};
-  int best = 64;
-  for (int i = 0; i < 4; ++i) {
-    const int bn = cands[i];
-    if ((Na % bn) || (Nb % bn) || (size_t)(TF_BM + bn) * K * 2 > TF_LDS_MAX) continue;
-    best = bn;
-    const long blocks = (long)(Na / bn) * ((Ma + rpba - 1) / rpba) + (long)(Nb / bn) * ((Mb + 31) / 32);
-    if (blocks <= 256) break;
-  }
-  return best;
-}
-
 // one AttentionLayer.  x_in: fp32 tokens of layer 0 (null for later layers: the input is then LN_ffn[layer-1](w.y)).
 template <typename T>
 int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv, const uint16_t* wp, const float* pp, int layer,
                   const TfDims& d, const TfWs& w, hipStream_t s, const float* merge_kv_motion = nullptr) {
-  const int M = d.B * d.T, D = d.D, dh = D / d.H;
-  // row blocks: two whole clips (T <= 16), one clip (T <= 32), or -- longer clips -- uniform 32-row blocks for the row-wise GEMMs
-  // and (clip, 32-query part) blocks for the two attention launches
-  const int cpb = d.T <= 16 ? 2 : 1, parts = d.T > 32 ? (d.T + 31) / 32 : 1, rpb = d.T > 32 ? 32 : cpb * d.T;
+  const TfamBlocks bk = tfam_blocks(d);
+  const bool pair = merge_kv_motion != nullptr && d.has_cross;
+  const TfamStep<TFAM_F_COUNT> plan = tfam_route_layer_fwd(d, bk, x_in != nullptr, pair, false, kNoOverrides);
+  if (plan.rc) return plan.rc;
+  const int M = bk.M, D = d.D, dh = bk.dh, cpb = bk.cpb, parts = bk.parts, rpb = bk.rpb;
   const float scale = 1.0f / sqrtf((float)dh);
   auto W = [&](int slot) { return wp + vmc_tfam_pack_offset(slot, layer, D, d.ff, d.L, d.C); };
   auto P = [&](int slot, int l) { return pp + vmc_tfam_pack_offset(slot, l, D, d.ff, d.L, d.C); };
@@ -183,38 +121,31 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
     a.W = W(VMC_TFAM_W_SELF_IN); a.ldw = D; a.bias = P(VMC_TFAM_P_SELF_IN_B, layer);
     a.out = w.qkv; a.ldo = 3 * D; a.act = VMC_ACT_NONE;
     a.frag[0] = w.qf; a.frag[1] = w.kf; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh;    // V columns stay row-major
-    a.frag_NTT = tf_ntt(d.T);
-    const bool pair = merge_kv_motion != nullptr && d.has_cross;
+    a.frag_NTT = bk.ntt_q;
     TfArgs b = {};
-    int bn = tf_pick_bn(M, a.N, rpb, D, false);
-    if (pair) {
-      b = tf_kv_layer_args(merge_kv_motion, wp, pp, layer, d, w);
-      bn = tf_pick_bn_pair(M, a.N, rpb, b.M, b.N, D);
-    }
+    if (pair) b = tf_kv_layer_args(merge_kv_motion, wp, pp, layer, d, w);
+    const TfamPlan& pl = plan.p[TFAM_F_QKV];
     if (x_in != nullptr) {
       a.A = x_in; a.lda = D;
-      rc = pair ? tf_qkv_kv_pair<T, PRO_F32>(a, b, bn, s) : tf_gemm_k<T, PRO_F32, EPI_ACT16>(a, bn, s);
+      rc = pair ? tf_run_pair<T, PRO_F32, false>(a, b, pl, s) : tf_run_single<T, PRO_F32, EPI_ACT16, false>(a, pl, s);
       resid = x_in;
     } else {
       a.A = w.y; a.lda = D; a.eps = 1e-5f;
       a.ln_g = P(VMC_TFAM_P_NORM_FFN, layer - 1); a.ln_b = a.ln_g + D; a.xout = w.xa;
-      rc = pair ? tf_qkv_kv_pair<T, PRO_LN>(a, b, bn, s) : tf_gemm_k<T, PRO_LN, EPI_ACT16>(a, bn, s);
+      rc = pair ? tf_run_pair<T, PRO_LN, false>(a, b, pl, s) : tf_run_single<T, PRO_LN, EPI_ACT16, false>(a, pl, s);
       resid = w.xa;
     }
     if (rc) return rc;
   }
-  auto keyrows = [](int tk) { return tk > 32 ? 64 : (tk > 16 ? 32 : 16); };
-  const int bn_attn = tf_pick_bn(M, D, rpb, D, true, (cpb - 1) * d.T + keyrows(d.T));
-  const int bn_cross = tf_pick_bn(M, D, rpb, D, true, (cpb - 1) * d.Tk + keyrows(d.Tk));
   {  // 2: y = resid + selfattn(qkv) Wo^T + b
     TfArgs a = {};
     a.M = M; a.N = D; a.K = D; a.rpb = rpb; a.cpb = cpb;
     a.q = w.qf; a.k = w.kf; a.v = w.qkv + 2 * D; a.ldv = 3 * D;
-    a.parts = parts; a.ntt_q = a.ntt_k = tf_ntt(d.T);
+    a.parts = parts; a.ntt_q = a.ntt_k = bk.ntt_q;
     a.kmask = mask; a.T = d.T; a.Tk = d.T; a.H = d.H; a.B = d.B; a.scale = scale;
     a.W = W(VMC_TFAM_W_SELF_OUT); a.ldw = D; a.bias = P(VMC_TFAM_P_SELF_OUT_B, layer);
     a.resid = resid; a.ldres = D; a.out = w.y; a.ldo = D;
-    if ((rc = (D == 768 ? tf_dispatch_attn<T, 768>(a, bn_attn, dh, s) : tf_dispatch_attn<T, 512>(a, bn_attn, dh, s)))) return rc;
+    if ((rc = tf_run_attn<T, false>(a, plan.p[TFAM_F_SELF], s))) return rc;
   }
   const float* ln_g = P(VMC_TFAM_P_NORM_SELF, layer);
   const float* x2 = nullptr;
@@ -225,19 +156,19 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
       a.A = w.y; a.lda = D; a.eps = 1e-5f; a.ln_g = ln_g; a.ln_b = ln_g + D; a.xout = w.xb;
       a.W = W(VMC_TFAM_W_CROSS_Q); a.ldw = D; a.bias = P(VMC_TFAM_P_CROSS_Q_B, layer);
       a.out = w.q; a.ldo = D; a.act = VMC_ACT_NONE;
-      a.frag[0] = w.qf; a.frag[1] = nullptr; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = tf_ntt(d.T);
-      if ((rc = tf_gemm_k<T, PRO_LN, EPI_ACT16>(a, tf_pick_bn(M, a.N, rpb, D, false), s))) return rc;
+      a.frag[0] = w.qf; a.frag[1] = nullptr; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = bk.ntt_q;
+      if ((rc = tf_run_single<T, PRO_LN, EPI_ACT16, false>(a, plan.p[TFAM_F_Q], s))) return rc;
     }
     {  // 4: y = xb + crossattn(q, K_l, V_l) Wo^T + b
       TfArgs a = {};
       a.M = M; a.N = D; a.K = D; a.rpb = rpb; a.cpb = cpb;
       a.q = w.qf;
       a.k = w.kxf + (size_t)layer * w.kxf_stride; a.v = w.kv + (size_t)layer * 2 * D + D; a.ldv = d.L * 2 * D;
-      a.parts = parts; a.ntt_q = tf_ntt(d.T); a.ntt_k = tf_ntt(d.Tk);
+      a.parts = parts; a.ntt_q = bk.ntt_q; a.ntt_k = bk.ntt_kx;
       a.kmask = mask_kv; a.T = d.T; a.Tk = d.Tk; a.H = d.H; a.B = d.B; a.scale = scale;
       a.W = W(VMC_TFAM_W_CROSS_OUT); a.ldw = D; a.bias = P(VMC_TFAM_P_CROSS_OUT_B, layer);
       a.resid = w.xb; a.ldres = D; a.out = w.y; a.ldo = D;
-      if ((rc = (D == 768 ? tf_dispatch_attn<T, 768>(a, bn_cross, dh, s) : tf_dispatch_attn<T, 512>(a, bn_cross, dh, s)))) return rc;
+      if ((rc = tf_run_attn<T, false>(a, plan.p[TFAM_F_CROSS], s))) return rc;
     }
     ln_g = P(VMC_TFAM_P_NORM_CROSS, layer);
   }
@@ -247,7 +178,7 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
     a.A = w.y; a.lda = D; a.eps = 1e-5f; a.ln_g = ln_g; a.ln_b = ln_g + D; a.xout = w.xa;
     a.W = W(VMC_TFAM_W_FFN0); a.ldw = D; a.bias = P(VMC_TFAM_P_FFN0_B, layer);
     a.out = w.h; a.ldo = d.ff; a.act = VMC_ACT_RELU;
-    if ((rc = tf_gemm_k<T, PRO_LN, EPI_ACT16>(a, tf_pick_bn(M, a.N, rpb, D, false), s))) return rc;
+    if ((rc = tf_run_single<T, PRO_LN, EPI_ACT16, false>(a, plan.p[TFAM_F_FFN0], s))) return rc;
     x2 = w.xa;
   }
   {  // 6: y = xa + h W2^T + b
@@ -256,7 +187,7 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
     a.A = w.h; a.lda = d.ff;
     a.W = W(VMC_TFAM_W_FFN3); a.ldw = d.ff; a.bias = P(VMC_TFAM_P_FFN3_B, layer);
     a.resid = x2; a.ldres = D; a.out = w.y; a.ldo = D;
-    if ((rc = tf_launch_ring<T, 16, 512, 3>(a, s))) return rc;
+    if ((rc = tf_run_ring<T, false>(a, plan.p[TFAM_F_FFN3], s))) return rc;
   }
   return 0;
 }
@@ -264,12 +195,12 @@ int tf_layer_impl(const float* x_in, const uint8_t* mask, const uint8_t* mask_kv
 template <typename T>
 int tf_head_impl(const uint16_t* wp, const float* pp, float* logits, const TfDims& d, const TfWs& w, const int* pool_len, hipStream_t s) {
   const int D = d.D;
+  const TfamStep<TFAM_H_COUNT> plan = tfam_route_head_fwd(d, false, kNoOverrides);
+  if (plan.rc) return plan.rc;
   const float* lnf = pp + vmc_tfam_pack_offset(VMC_TFAM_P_NORM_FFN, d.L - 1, D, d.ff, d.L, d.C);
   const float* lnc = pp + vmc_tfam_pack_offset(VMC_TFAM_P_CLS_LN, 0, D, d.ff, d.L, d.C);
-  if (D == 768) hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f, pool_len);
-  else hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(d.B), dim3(256), 0, s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, 1e-5f, pool_len);
-  VMC_CHECK_LAUNCH();
   int rc;
+  if ((rc = tf_run_pool<T>(plan.p[TFAM_H_POOL], s, w.y, lnf, lnf + D, lnc, lnc + D, w.pool, d.T, pool_len))) return rc;
   {
     TfArgs a = {};
     a.M = d.B; a.N = D / 2; a.K = D; a.rpb = 32;
@@ -277,7 +208,7 @@ int tf_head_impl(const uint16_t* wp, const float* pp, float* logits, const TfDim
     a.W = wp + vmc_tfam_pack_offset(VMC_TFAM_W_CLS1, 0, D, d.ff, d.L, d.C); a.ldw = D;
     a.bias = pp + vmc_tfam_pack_offset(VMC_TFAM_P_CLS1_B, 0, D, d.ff, d.L, d.C);
     a.out = w.g; a.ldo = D / 2; a.act = VMC_ACT_GELU_ERF;
-    if ((rc = tf_gemm_k<T, PRO_16, EPI_ACT16>(a, 16, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_16, EPI_ACT16, false>(a, plan.p[TFAM_H_CLS1], s))) return rc;
   }
   {
     TfArgs a = {};
@@ -286,7 +217,7 @@ int tf_head_impl(const uint16_t* wp, const float* pp, float* logits, const TfDim
     a.W = wp + vmc_tfam_pack_offset(VMC_TFAM_W_CLS4, 0, D, d.ff, d.L, d.C); a.ldw = D / 2;
     a.bias = pp + vmc_tfam_pack_offset(VMC_TFAM_P_CLS4_B, 0, D, d.ff, d.L, d.C);
     a.out = logits; a.ldo = d.C;
-    if ((rc = tf_gemm_k<T, PRO_16, EPI_BIAS32>(a, 16, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_16, EPI_BIAS32, false>(a, plan.p[TFAM_H_CLS4], s))) return rc;
   }
   return 0;
 }
@@ -309,7 +240,13 @@ extern "C" int vmc_tfam_fold_layernorm(const float* W, const float* bias, const 
 
 extern "C" size_t vmc_tfam_workspace_bytes(int B, int T, int Tk, int D, int ff, int L, int C, int has_cross) {
   TfDims d = {B, T, Tk, D, 8, ff, L, C, has_cross};      // the head count does not change any size (frag buffers: B * D * 32 elements)
-  return tf_ws(nullptr, d).bytes;
+  return tfam_workspace_bytes(d);
+}
+
+// host only: 0 when the fused chain (train: the training chains) takes these shapes, else the error every entry below returns
+extern "C" int vmc_tfam_supported(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int train) {
+  TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
+  return tfam_check(d, train != 0);
 }
 
 #define TF_DT(call)                                   \
@@ -320,7 +257,7 @@ extern "C" size_t vmc_tfam_workspace_bytes(int B, int T, int Tk, int D, int ff, 
 extern "C" int vmc_tfam_kv_fwd(const float* motion, const void* wpack, const float* ppack, void* ws, size_t ws_bytes, int B, int T, int Tk,
                                int D, int H, int ff, int L, int C, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, 1};
-  if (int rc = tf_check(d)) return rc;
+  if (int rc = tfam_check(d, false)) return rc;
   const TfWs w = tf_ws(ws, d);
   if (ws == nullptr || ws_bytes < w.bytes) return VMC_E_ARG;
   if (dtype16 == VMC_BF16) return tf_kv_impl<BF16>(motion, (const uint16_t*)wpack, ppack, d, w, (hipStream_t)stream);
@@ -332,7 +269,7 @@ extern "C" int vmc_tfam_layer_fwd(const float* x_in, const uint8_t* mask, const 
                                   int layer, void* ws, size_t ws_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
                                   int has_cross, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
-  if (int rc = tf_check(d)) return rc;
+  if (int rc = tfam_check(d, false)) return rc;
   if (layer < 0 || layer >= L || (layer == 0) != (x_in != nullptr)) return VMC_E_ARG;
   const TfWs w = tf_ws(ws, d);
   if (ws == nullptr || ws_bytes < w.bytes) return VMC_E_ARG;
@@ -346,7 +283,7 @@ extern "C" int vmc_tfam_layer_fwd(const float* x_in, const uint8_t* mask, const 
 extern "C" int vmc_tfam_head_fwd_len(const void* wpack, const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D,
                                      int H, int ff, int L, int C, int has_cross, const int* pool_len, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
-  if (int rc = tf_check(d)) return rc;
+  if (int rc = tfam_check(d, false)) return rc;
   const TfWs w = tf_ws(ws, d);
   if (ws == nullptr || ws_bytes < w.bytes) return VMC_E_ARG;
   if (dtype16 == VMC_BF16) return tf_head_impl<BF16>((const uint16_t*)wpack, ppack, logits, d, w, pool_len, (hipStream_t)stream);
@@ -363,7 +300,7 @@ extern "C" int vmc_tfam_forward_len(const float* x, const float* motion, const u
                                     const float* ppack, float* logits, void* ws, size_t ws_bytes, int B, int T, int Tk, int D, int H, int ff,
                                     int L, int C, int has_cross, const int* pool_len, int dtype16, void* stream) {
   TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
-  if (int rc = tf_check(d)) return rc;
+  if (int rc = tfam_check(d, false)) return rc;
   if (!x || !wpack || !ppack || !logits || (has_cross && !motion)) return VMC_E_ARG;
   const TfWs w = tf_ws(ws, d);
   if (ws == nullptr || ws_bytes < w.bytes) return VMC_E_ARG;

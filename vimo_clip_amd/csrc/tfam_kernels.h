@@ -1,16 +1,11 @@
 // Device code and launch helpers of the fused TFAM chains (gfx950): tfam_fused.hip (eval forward, folded LayerNorm weights)
-// and tfam_train.hip (training forward + backward) instantiate what they need from here.
+// and tfam_train.hip (training forward + backward) instantiate what they need from here.  What is launched when, and the constants
+// both sides share, are in tfam_route.h.
 #pragma once
 #include "common.h"
+#include "tfam_route.h"
 
 namespace {
-
-constexpr int TF_BM = 32;
-constexpr int TF_NTH = 256;
-constexpr int TF_MAX_T = 64;      // tokens per clip (queries in parts of 32 per row block, up to four key tiles)
-
-enum { PRO_F32 = 0, PRO_LN = 1, PRO_16 = 2, PRO_ATTN = 3, PRO_LNBWD = 4 };
-enum { EPI_ACT16 = 0, EPI_RESID32 = 1, EPI_BIAS32 = 2 };
 
 struct TfArgs {
   const void* A;            // PRO_F32 / PRO_LN: float [M, lda]; PRO_16: 16-bit [M, lda]
@@ -91,14 +86,10 @@ __device__ __forceinline__ int tf_grow(const TfArgs& a, int rb, int lrow, bool& 
 // sit at lane (16 qq + r) x 16 B of a 1-KiB record per (clip, head, token tile, kk) -- one fully coalesced wave load per
 // fragment, where row-major [token][feature] rows give 16 rows x 64 B per instruction (measured: the fragment-shaped loads
 // of 2 (clip, head) pairs cost 3.7 us of a 9.9 us launch).  Element offset of (clip, head, token t, head-dim d):
-// NTT = token tiles of 16 per (clip, head): tf_ntt(T) = max(2, ceil(T / 16)) (clips of up to 32 tokens keep the two-tile records).
-__host__ __device__ __forceinline__ int tf_ntt(int T) { return T <= 32 ? 2 : (T + 15) >> 4; }
+// NTT = token tiles of 16 per (clip, head): tf_ntt(T) = max(2, ceil(T / 16)) (tfam_route.h).
 __host__ __device__ __forceinline__ size_t tf_frag_off(int clip, int head, int t, int d, int H, int DH, int NTT = 2) {
   const int KK = DH >> 5;
   return ((((size_t)(clip * H + head) * NTT + (t >> 4)) * KK + (d >> 5)) * 64 + ((d >> 3) & 3) * 16 + (t & 15)) * 8 + (d & 7);
-}
-__host__ __device__ __forceinline__ size_t tf_frag_elems(int clips, int H, int DH, int NTT = 2) {
-  return (size_t)clips * H * NTT * (DH >> 5) * 512;
 }
 
 // (n tile, row block) of a block id: blocks that share a W tile agree mod 8 -> same XCD (round-robin dispatch).
@@ -959,135 +950,126 @@ __global__ void __launch_bounds__(256) tf_fold_ln_kernel(const float* __restrict
   if (lane == 0) bias_out[row] = bias[row] + acc;
 }
 
-// ---- host side ---------------------------------------------------------------------------------------------------------
-constexpr size_t TF_LDS_MAX = 160 * 1024;
-
-constexpr int TF_NW = 8;       // waves per workgroup of the single-shot kernels (2 row tiles x 4 K slices)
-
-template <int BN, int PRO, int KD, int NKT>
-constexpr size_t tf_lds_bytes(int cpb, int Tk) {
-  if (PRO == PRO_ATTN && NKT > 2) {              // V and W share a region (LATEW)
-    const size_t v = (size_t)((cpb - 1) * Tk + 16 * NKT) * KD * 2 + 1024, w = (size_t)BN * KD * 2;
-    return (size_t)TF_BM * KD * 2 + (v > w ? v : w);
-  }
-  return (size_t)(TF_BM + BN) * KD * 2 +
-         (PRO == PRO_ATTN ? (size_t)((cpb - 1) * Tk + 16 * NKT) * KD * 2 + 1024 : 0);    // + one LDS-DMA piece of slack
-}
-
+// ---- host side: launching the plans of tfam_route.h ---------------------------------------------------------------------------
+// Each tf_launch* takes the plan's grid, block and LDS; its first line asserts that the plan is one of this instantiation (after
+// tfam_check no chain reaches these returns).
 template <typename T, int BN, int PRO, int EPI, int KD, int DH, int QT, int NKT = 1, bool TR = false>
-int tf_launch(TfArgs& a, hipStream_t s) {
-  const size_t lds = tf_lds_bytes<BN, PRO, KD, NKT>(a.cpb, a.Tk);
-  if (lds > TF_LDS_MAX || a.K != KD) return VMC_E_SHAPE;
-  if ((TF_NW / 2 - 1) * 2 * (BN / 16) * 1024 > TF_BM * KD * 2) return VMC_E_SHAPE;      // K-slice exchange must fit the A image
-  a.n_tiles = (a.N + BN - 1) / BN;
-  a.n_rb = (PRO == PRO_ATTN && a.parts > 1) ? a.B * a.parts : (a.M + a.rpb - 1) / a.rpb;
+int tf_launch(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if ((size_t)p.lds != tfam_lds_bytes(BN, PRO == PRO_ATTN, KD, NKT, a.cpb, a.Tk) || (size_t)p.lds > TF_LDS_MAX || a.K != KD) return VMC_E_SHAPE;
+  a.n_tiles = p.n_tiles;
+  a.n_rb = p.n_rb;
   auto kern = tf_gemm_kernel<T, BN, PRO, EPI, KD, DH, QT, NKT, TF_NW, TR>;
   static bool attr_done = false;                // per instantiation
   if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
-  hipLaunchKernelGGL(kern, dim3(a.n_tiles * a.n_rb), dim3(64 * TF_NW), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, a);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int BN, int PRO, int EPI, int KD, bool TR = false>
-int tf_launch_pair(TfArgs& a, TfArgs& b, hipStream_t s) {
-  const size_t lds = tf_lds_bytes<BN, PRO, KD, 1>(1, 0);
-  if (lds > TF_LDS_MAX || a.K != KD || b.K != KD) return VMC_E_SHAPE;
-  a.n_tiles = (a.N + BN - 1) / BN; a.n_rb = (a.M + a.rpb - 1) / a.rpb;
-  b.n_tiles = (b.N + BN - 1) / BN; b.n_rb = (b.M + b.rpb - 1) / b.rpb;
+int tf_launch_pair(TfArgs& a, TfArgs& b, const TfamPlan& p, hipStream_t s) {
+  if ((size_t)p.lds != tfam_lds_bytes(BN, false, KD, 1, 1, 0) || (size_t)p.lds > TF_LDS_MAX || a.K != KD || b.K != KD) return VMC_E_SHAPE;
+  a.n_tiles = p.n_tiles; a.n_rb = p.n_rb;
+  b.n_tiles = p.n_tiles_b; b.n_rb = p.n_rb_b;
   auto kern = tf_gemm_pair_kernel<T, BN, PRO, EPI, KD, TF_NW, TR>;
   static bool attr_done = false;
   if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
-  const int na = a.n_tiles * a.n_rb;
-  hipLaunchKernelGGL(kern, dim3(na + b.n_tiles * b.n_rb), dim3(64 * TF_NW), lds, s, a, b, na);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, a, b, a.n_tiles * a.n_rb);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 template <typename T, int BN, int KC, int NST, bool TR = false>
-int tf_launch_ring(TfArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)NST * (TF_BM + BN) * KC * 2 + 2 * (BN / 16) * 1024;
-  if (lds > TF_LDS_MAX || a.K % KC) return VMC_E_SHAPE;
-  a.n_tiles = (a.N + BN - 1) / BN;
-  a.n_rb = (a.M + a.rpb - 1) / a.rpb;
+int tf_launch_ring(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if ((size_t)p.lds > TF_LDS_MAX || a.K % KC) return VMC_E_SHAPE;
+  a.n_tiles = p.n_tiles;
+  a.n_rb = p.n_rb;
   auto kern = tf_gemm_ring_kernel<T, BN, KC, NST, TR>;
   static bool attr_done = false;
   if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
-  hipLaunchKernelGGL(kern, dim3(a.n_tiles * a.n_rb), dim3(TF_NTH), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(p.grid), dim3(p.block), p.lds, s, a);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
-// Output-column tile.  A workgroup's cost is one memory round trip plus (32 A rows + BN W rows) x K bytes at the ~70 GB/s one
-// CU pulls from L2, whatever BN is; what BN decides is how many workgroups there are.  Take the narrowest tile (most CUs
-// streaming W) whose grid still fits one resident round (2 workgroups per CU while the LDS footprint allows, else 1).
-inline int tf_pick_bn(int M, int N, int rpb, int K, bool attn, int vrows = 48) {
-  const int n_rb = (M + rpb - 1) / rpb;
-  const int cands[4] = {16, 32, 48, 64};
-  int best = 16;
-  for (int i = 0; i < 4; ++i) {
-    const int bn = cands[i];
-    if (N % bn && !(N < bn)) continue;
-    if (attn && bn > 32) break;
-    if (attn && vrows > 48 && bn > 16) break;    // more than 32 keys: the 16-column kernels (V and W share a region)
-    const size_t lds = (attn && vrows > 48) ? (size_t)TF_BM * K * 2 + (size_t)vrows * K * 2 + 1024
-                                             : (size_t)(TF_BM + bn) * K * 2 + (attn ? (size_t)vrows * K * 2 + 1024 : 0);
-    if (lds > TF_LDS_MAX) break;
-    best = bn;
-    const int per_cu = lds <= 80 * 1024 ? 2 : 1;
-    if ((long)((N + bn - 1) / bn) * n_rb <= 256L * per_cu) break;
+// The ladders from a plan's fields to its instantiation, one per family, for both chains (TR).  The training chain has no BN = 48
+// kernel, 16-column attention only, 32- / 64-column pairs only, and alone has the KC = 384 ring.
+template <typename T, int PRO, int EPI, int KD, bool TR>
+int tf_run_bn(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  switch (p.bn) {
+    case 64: return tf_launch<T, 64, PRO, EPI, KD, 64, 1, 1, TR>(a, p, s);
+    case 48: if constexpr (!TR) return tf_launch<T, 48, PRO, EPI, KD, 64, 1, 1, TR>(a, p, s); else return VMC_E_SHAPE;
+    case 32: return tf_launch<T, 32, PRO, EPI, KD, 64, 1, 1, TR>(a, p, s);
+    case 16: return tf_launch<T, 16, PRO, EPI, KD, 64, 1, 1, TR>(a, p, s);
+    default: return VMC_E_SHAPE;
   }
-  return best;
+}
+template <typename T, int PRO, int EPI, bool TR>
+int tf_run_single(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if (p.rc) return p.rc;
+  switch (p.kd) {
+    case 768: return tf_run_bn<T, PRO, EPI, 768, TR>(a, p, s);
+    case 512: return tf_run_bn<T, PRO, EPI, 512, TR>(a, p, s);
+    case 384: if constexpr (PRO == PRO_16) return tf_run_bn<T, PRO, EPI, 384, TR>(a, p, s); else return VMC_E_SHAPE;
+    case 256: if constexpr (PRO == PRO_16) return tf_run_bn<T, PRO, EPI, 256, TR>(a, p, s); else return VMC_E_SHAPE;
+    default: return VMC_E_SHAPE;
+  }
 }
 
-#define TF_BN_SWITCH(bn, CALL)            \
-  switch (bn) {                           \
-    case 64: return CALL(64);             \
-    case 48: return CALL(48);             \
-    case 32: return CALL(32);             \
-    default: return CALL(16);             \
-  }
-
-template <typename T, int PRO, int EPI, int KD>
-int tf_dispatch_bn(TfArgs& a, int bn, hipStream_t s) {
-#define TF_CALL(BNV) tf_launch<T, BNV, PRO, EPI, KD, 64, 1>(a, s)
-  TF_BN_SWITCH(bn, TF_CALL)
-#undef TF_CALL
-}
-
-template <typename T, int KD, int BN, int DH>
-int tf_dispatch_attn3(TfArgs& a, hipStream_t s) {
-  const int qt = a.T > 16 ? 2 : 1, nkt = a.Tk > 32 ? 4 : (a.Tk > 16 ? 2 : 1);
-  if (nkt == 4) {
-    if constexpr (BN == 16) return qt == 1 ? tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 1, 4>(a, s) : tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 2, 4>(a, s);
+template <typename T, int KD, int BN, int DH, bool TR>
+int tf_run_attn3(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if (p.nkt == 4) {
+    if constexpr (BN == 16) return p.qt == 1 ? tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 1, 4, TR>(a, p, s) : tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 2, 4, TR>(a, p, s);
     else return VMC_E_SHAPE;
   }
-  if (qt == 1 && nkt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 1, 1>(a, s);
-  if (qt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 1, 2>(a, s);
-  if (nkt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 2, 1>(a, s);
-  return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 2, 2>(a, s);
+  if (p.qt == 1 && p.nkt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 1, 1, TR>(a, p, s);
+  if (p.qt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 1, 2, TR>(a, p, s);
+  if (p.nkt == 1) return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 2, 1, TR>(a, p, s);
+  return tf_launch<T, BN, PRO_ATTN, EPI_RESID32, KD, DH, 2, 2, TR>(a, p, s);
+}
+template <typename T, int KD, bool TR>
+int tf_run_attn2(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if constexpr (!TR)
+    if (p.bn == 32) return p.dh == 64 ? tf_run_attn3<T, KD, 32, 64, TR>(a, p, s) : tf_run_attn3<T, KD, 32, 96, TR>(a, p, s);
+  if (p.bn != 16) return VMC_E_SHAPE;
+  return p.dh == 64 ? tf_run_attn3<T, KD, 16, 64, TR>(a, p, s) : tf_run_attn3<T, KD, 16, 96, TR>(a, p, s);
+}
+template <typename T, bool TR>
+int tf_run_attn(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if (p.rc) return p.rc;
+  return p.kd == 768 ? tf_run_attn2<T, 768, TR>(a, p, s) : tf_run_attn2<T, 512, TR>(a, p, s);
 }
 
-template <typename T, int KD>
-int tf_dispatch_attn(TfArgs& a, int bn, int dh, hipStream_t s) {
-  if (bn == 32) return dh == 64 ? tf_dispatch_attn3<T, KD, 32, 64>(a, s) : tf_dispatch_attn3<T, KD, 32, 96>(a, s);
-  return dh == 64 ? tf_dispatch_attn3<T, KD, 16, 64>(a, s) : tf_dispatch_attn3<T, KD, 16, 96>(a, s);
+// two problems (a layer's qkv projection and its cross-attention K|V projection) in ONE launch
+template <typename T, int PRO, bool TR>
+int tf_run_pair(TfArgs& a, TfArgs& b, const TfamPlan& p, hipStream_t s) {
+  if (p.rc) return p.rc;
+#define TF_PAIR(BNV) (p.kd == 768 ? tf_launch_pair<T, BNV, PRO, EPI_ACT16, 768, TR>(a, b, p, s) : tf_launch_pair<T, BNV, PRO, EPI_ACT16, 512, TR>(a, b, p, s))
+  switch (p.bn) {
+    case 64: return TF_PAIR(64);
+    case 48: if constexpr (!TR) return TF_PAIR(48); else return VMC_E_SHAPE;
+    case 32: return TF_PAIR(32);
+    case 16: if constexpr (!TR) return TF_PAIR(16); else return VMC_E_SHAPE;
+    default: return VMC_E_SHAPE;
+  }
+#undef TF_PAIR
 }
 
-struct TfDims {
-  int B, T, Tk, D, H, ff, L, C, has_cross;
-};
+template <typename T, bool TR>
+int tf_run_ring(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if (p.rc) return p.rc;
+  if (p.kc == TF_RING_KC) return tf_launch_ring<T, TF_RING_BN, TF_RING_KC, TF_RING_NST, TR>(a, p, s);
+  if constexpr (TR)
+    if (p.kc == TR_RING_KC_ALT) return tf_launch_ring<T, TF_RING_BN, TR_RING_KC_ALT, TF_RING_NST, TR>(a, p, s);
+  return VMC_E_SHAPE;
+}
 
-inline int tf_check(const TfDims& d) {
-  if (d.B <= 0 || d.T <= 0 || d.T > TF_MAX_T || d.L <= 0 || d.C <= 0) return VMC_E_SHAPE;
-  if (d.D != 512 && d.D != 768) return VMC_E_SHAPE;
-  if (d.H <= 0 || d.D % d.H) return VMC_E_SHAPE;
-  const int dh = d.D / d.H;
-  if (dh != 64 && dh != 96) return VMC_E_SHAPE;
-  if (d.ff % 512 || d.ff <= 0) return VMC_E_SHAPE;
-  if (d.has_cross && (d.Tk <= 0 || d.Tk > TF_MAX_T)) return VMC_E_SHAPE;
-  const int cpb = d.T <= 16 ? 2 : 1;
-  if ((cpb * d.H) % 4) return VMC_E_SHAPE;
+template <typename T>
+int tf_run_pool(const TfamPlan& p, hipStream_t s, const float* y, const float* g1, const float* b1, const float* g2, const float* b2, uint16_t* out,
+                int Tn, const int* pool_len, float* pooled32 = nullptr) {
+  if (p.kd == 768) hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(p.grid), dim3(p.block), 0, s, y, g1, b1, g2, b2, out, Tn, 1e-5f, pool_len, pooled32);
+  else hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(p.grid), dim3(p.block), 0, s, y, g1, b1, g2, b2, out, Tn, 1e-5f, pool_len, pooled32);
+  VMC_CHECK_LAUNCH();
   return 0;
 }
 

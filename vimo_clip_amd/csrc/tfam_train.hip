@@ -26,219 +26,19 @@
 
 namespace {
 
-struct TrDims {
-  int B, T, Tk, D, H, ff, L, C, has_cross;
-};
-
-inline int tr_check(const TrDims& d) {
-  TfDims e = {d.B, d.T, d.Tk, d.D, d.H, d.ff, d.L, d.C, d.has_cross};
-  if (int rc = tf_check(e)) return rc;
-  if (d.B * d.T > 256 || (d.has_cross && d.B * d.Tk > 256)) return VMC_E_SHAPE;      // the grouped weight gradient holds <= 4 token stages
-  if (d.C % 4 || d.B > 32) return VMC_E_SHAPE;
-  return 0;
-}
-
-// ---- workspace ----------------------------------------------------------------------------------------------------------
-struct TrLayerWs {
-  // saved by the forward
-  float* xin32;             // layer > 0: LN_ffn[l-1](y3[l-1]) (the residual operand; layer 0 uses the caller's tokens)
-  uint16_t* x0_16;          // 16-bit rows fed to the qkv GEMM
-  uint16_t* qkv16;          // [M, 3D]
-  uint16_t* o_self;         // [M, D]
-  float* lse_self;          // [B, H, T]
-  float* y1;                // pre-norm sums (fp32)
-  uint8_t* keep1;
-  float* x1_32;
-  uint16_t* x1_16;
-  uint16_t* q16;            // [M, D]
-  uint16_t* kv16;           // [Mk, 2D]
-  uint16_t* o_cross;
-  float* lse_cross;
-  float* y2;
-  uint8_t* keep2;
-  float* x2_32;
-  uint16_t* x2_16;
-  uint16_t* h16;            // [M, ff] after ReLU and dropout
-  float* y3;
-  uint8_t* keep3;
-  // backward
-  float *dx3, *dy3, *dx2, *dy2, *dx1, *dy1;
-  uint16_t *d3_16, *dh16, *d2_16, *doc16, *dq16, *dkv16, *d1_16, *dos16, *dqkv16;
-  float *st3, *st2, *st1;   // [M, 2] mean, rstd
-  float* attn_ws;
-};
-struct TrWs {
-  uint16_t* motion16;       // [Mk, D]
-  uint16_t *qf, *kf, *kxf;  // fragment-major q / k operands of the fused attention prologues (forward-only)
-  float* pooled32;          // [B, D]
-  uint16_t* pool16;         // [B, D]   LN_cls(pooled) 16-bit
-  uint16_t* a16;            // [B, D/2] classifier.1 pre-activation
-  uint16_t* g16;            // [B, D/2] drop(gelu(a))
-  float* da;                // [B, D/2]
-  float* dpl;               // [B, D]   gradient wrt LN_cls(pooled)
-  char* layers;
-  size_t layer_bytes;
-  size_t bytes;
-};
-
-inline size_t tr_al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline TrLayerWs tr_layer_ws(char* base, const TrDims& d, size_t* bytes_out = nullptr) {
-  const size_t M = (size_t)d.B * d.T, Mk = (size_t)d.B * (d.has_cross ? d.Tk : 0), D = d.D, ff = d.ff;
-  TrLayerWs w;
-  size_t o = 0;
-  auto take = [&](size_t n) { char* p = base + o; o += tr_al(n); return p; };
-  w.xin32 = (float*)take(M * D * 4);
-  w.x0_16 = (uint16_t*)take(M * D * 2);
-  w.qkv16 = (uint16_t*)take(M * 3 * D * 2);
-  w.o_self = (uint16_t*)take(M * D * 2);
-  w.lse_self = (float*)take((size_t)d.B * d.H * d.T * 4);
-  w.y1 = (float*)take(M * D * 4);
-  w.keep1 = (uint8_t*)take(M * D);
-  w.x1_32 = (float*)take(M * D * 4);
-  w.x1_16 = (uint16_t*)take(M * D * 2);
-  w.q16 = (uint16_t*)take(M * D * 2);
-  w.kv16 = (uint16_t*)take(Mk * 2 * D * 2);
-  w.o_cross = (uint16_t*)take(M * D * 2);
-  w.lse_cross = (float*)take((size_t)d.B * d.H * d.T * 4);
-  w.y2 = (float*)take(M * D * 4);
-  w.keep2 = (uint8_t*)take(M * D);
-  w.x2_32 = (float*)take(M * D * 4);
-  w.x2_16 = (uint16_t*)take(M * D * 2);
-  w.h16 = (uint16_t*)take(M * ff * 2);
-  w.y3 = (float*)take(M * D * 4);
-  w.keep3 = (uint8_t*)take(M * D);
-  w.dx3 = (float*)take(M * D * 4);
-  w.dy3 = (float*)take(M * D * 4);
-  w.dx2 = (float*)take(M * D * 4);
-  w.dy2 = (float*)take(M * D * 4);
-  w.dx1 = (float*)take(M * D * 4);
-  w.dy1 = (float*)take(M * D * 4);
-  w.d3_16 = (uint16_t*)take(M * D * 2);
-  w.dh16 = (uint16_t*)take(M * ff * 2);
-  w.d2_16 = (uint16_t*)take(M * D * 2);
-  w.doc16 = (uint16_t*)take(M * D * 2);
-  w.dq16 = (uint16_t*)take(M * D * 2);
-  w.dkv16 = (uint16_t*)take(Mk * 2 * D * 2);
-  w.d1_16 = (uint16_t*)take(M * D * 2);
-  w.dos16 = (uint16_t*)take(M * D * 2);
-  w.dqkv16 = (uint16_t*)take(M * 3 * D * 2);
-  w.st3 = (float*)take(M * 2 * 4);
-  w.st2 = (float*)take(M * 2 * 4);
-  w.st1 = (float*)take(M * 2 * 4);
-  w.attn_ws = (float*)take((size_t)d.B * d.H * d.T * 4);
-  if (bytes_out) *bytes_out = o;
-  return w;
-}
-
-inline TrWs tr_ws(void* base, const TrDims& d) {
-  const size_t Mk = (size_t)d.B * (d.has_cross ? d.Tk : 0), D = d.D;
-  char* p = (char*)base;
-  TrWs w;
-  size_t o = 0;
-  auto take = [&](size_t n) { char* q = p + o; o += tr_al(n); return q; };
-  w.motion16 = (uint16_t*)take(Mk * D * 2);
-  const size_t fe = tf_frag_elems(d.B, d.H, d.D / d.H, tf_ntt(d.T > d.Tk ? d.T : d.Tk));
-  w.qf = (uint16_t*)take(fe * 2);
-  w.kf = (uint16_t*)take(fe * 2);
-  w.kxf = (uint16_t*)take(fe * 2);
-  w.pooled32 = (float*)take((size_t)d.B * D * 4);
-  w.pool16 = (uint16_t*)take((size_t)d.B * D * 2);
-  w.a16 = (uint16_t*)take((size_t)d.B * (D / 2) * 2);
-  w.g16 = (uint16_t*)take((size_t)d.B * (D / 2) * 2);
-  w.da = (float*)take((size_t)d.B * (D / 2) * 4);
-  w.dpl = (float*)take((size_t)d.B * D * 4);
-  tr_layer_ws(nullptr, d, &w.layer_bytes);
-  w.layers = p + o;
-  o += (size_t)d.L * w.layer_bytes;
-  w.bytes = o;
-  return w;
-}
-inline TrLayerWs tr_lw(const TrWs& w, const TrDims& d, int layer) { return tr_layer_ws(w.layers + (size_t)layer * w.layer_bytes, d); }
-
-// ---- launch helpers (training instantiations; column tiles 16 / 32 / 64) ---------------------------------------------------
-// heavy: a LayerNorm (backward) prologue re-reads 32 fp32 rows (and more) per workgroup -- one workgroup per CU, wider tiles
-inline int tr_pick_bn(int M, int N, int rpb, int K, bool attn, bool heavy = false) {
-  if (attn) return 16;
-  static const int force_ff = getenv("VMC_TR_BN_FF") ? atoi(getenv("VMC_TR_BN_FF")) : 0;      // builder A/B switch
-  static const int force_d = getenv("VMC_TR_BN_D") ? atoi(getenv("VMC_TR_BN_D")) : 0;
-  if (heavy && force_ff && N >= 1024 && N % force_ff == 0) return force_ff;
-  if (heavy && force_d && N < 1024 && N % force_d == 0) return force_d;
-  const int n_rb = (M + rpb - 1) / rpb;
-  const int cands[3] = {16, 32, 64};
-  int best = 16;
-  for (int i = 0; i < 3; ++i) {
-    const int bn = cands[i];
-    if (N % bn) continue;
-    const size_t lds = (size_t)(TF_BM + bn) * K * 2;
-    if (lds > TF_LDS_MAX) break;
-    best = bn;
-    const int per_cu = (lds <= 80 * 1024 && !heavy) ? 2 : 1;
-    if ((long)(N / bn) * n_rb <= 256L * per_cu) break;
-  }
-  return best;
-}
-
-template <typename T, int PRO, int EPI, int KD>
-int tr_dispatch_bn(TfArgs& a, int bn, hipStream_t s) {
-  switch (bn) {
-    case 64: return tf_launch<T, 64, PRO, EPI, KD, 64, 1, 1, true>(a, s);
-    case 32: return tf_launch<T, 32, PRO, EPI, KD, 64, 1, 1, true>(a, s);
-    default: return tf_launch<T, 16, PRO, EPI, KD, 64, 1, 1, true>(a, s);
-  }
-}
-template <typename T, int PRO, int EPI>
-int tr_gemm(TfArgs& a, hipStream_t s) {
-  const int bn = tr_pick_bn(a.M, a.N, a.rpb, a.K, false, PRO == PRO_LN || PRO == PRO_LNBWD);
-  if (bn != 16 && a.N % bn) return VMC_E_SHAPE;      // a ragged last tile (140 classes) only at the 16-column tile
-  switch (a.K) {
-    case 768: return tr_dispatch_bn<T, PRO, EPI, 768>(a, bn, s);
-    case 512: return tr_dispatch_bn<T, PRO, EPI, 512>(a, bn, s);
-    case 384: if constexpr (PRO == PRO_16) return tr_dispatch_bn<T, PRO, EPI, 384>(a, bn, s); else return VMC_E_SHAPE;
-    case 256: if constexpr (PRO == PRO_16) return tr_dispatch_bn<T, PRO, EPI, 256>(a, bn, s); else return VMC_E_SHAPE;
-    default: return VMC_E_SHAPE;
-  }
-}
-template <typename T, int KD, int DH>
-int tr_attn3(TfArgs& a, hipStream_t s) {
-  const int qt = a.T > 16 ? 2 : 1, nkt = a.Tk > 32 ? 4 : (a.Tk > 16 ? 2 : 1);
-  if (nkt == 4) return qt == 1 ? tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 1, 4, true>(a, s) : tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 2, 4, true>(a, s);
-  if (qt == 1 && nkt == 1) return tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 1, 1, true>(a, s);
-  if (qt == 1) return tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 1, 2, true>(a, s);
-  if (nkt == 1) return tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 2, 1, true>(a, s);
-  return tf_launch<T, 16, PRO_ATTN, EPI_RESID32, KD, DH, 2, 2, true>(a, s);
-}
-template <typename T>
-int tr_attn(TfArgs& a, int dh, hipStream_t s) {
-  if (a.K == 768) return dh == 64 ? tr_attn3<T, 768, 64>(a, s) : tr_attn3<T, 768, 96>(a, s);
-  return dh == 64 ? tr_attn3<T, 512, 64>(a, s) : tr_attn3<T, 512, 96>(a, s);
-}
-template <typename T, int PRO>
-int tr_pair(TfArgs& a, TfArgs& b, hipStream_t s) {
-  // widest tile that keeps both problems inside one resident round; 64 when none does
-  int bn = 64;
-  for (int c = 32; c <= 64; c *= 2) {
-    if ((a.N % c) || (b.N % c)) continue;
-    const long blocks = (long)(a.N / c) * ((a.M + a.rpb - 1) / a.rpb) + (long)(b.N / c) * ((b.M + 31) / 32);
-    if (blocks <= 256) { bn = c; break; }
-  }
-  if ((a.N % bn) || (b.N % bn)) return VMC_E_SHAPE;
-  if (a.K == 768) return bn == 64 ? tf_launch_pair<T, 64, PRO, EPI_ACT16, 768, true>(a, b, s) : tf_launch_pair<T, 32, PRO, EPI_ACT16, 768, true>(a, b, s);
-  return bn == 64 ? tf_launch_pair<T, 64, PRO, EPI_ACT16, 512, true>(a, b, s) : tf_launch_pair<T, 32, PRO, EPI_ACT16, 512, true>(a, b, s);
-}
-template <typename T>
-int tr_ring(TfArgs& a, hipStream_t s) {
-  if (a.K % 512 == 0) return tf_launch_ring<T, 16, 512, 3, true>(a, s);
-  if (a.K % 384 == 0) return tf_launch_ring<T, 16, 384, 3, true>(a, s);
-  return VMC_E_SHAPE;
+const TfamOverrides& tr_overrides() {      // the A/B switches: read once per process
+  static const TfamOverrides ov = tfam_overrides_from_env();
+  return ov;
 }
 
 // ---- forward of one layer ------------------------------------------------------------------------------------------------
 template <typename T>
 int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
-                 int layer, const TrDims& d, const TrWs& ws, float p, const uint64_t* seeds, hipStream_t s) {
-  const int M = d.B * d.T, D = d.D, dh = D / d.H;
-  const int cpb = d.T <= 16 ? 2 : 1, parts = d.T > 32 ? (d.T + 31) / 32 : 1, rpb = d.T > 32 ? 32 : cpb * d.T;
+                 int layer, const TfDims& d, const TrWs& ws, float p, const uint64_t* seeds, hipStream_t s) {
+  const TfamBlocks bk = tfam_blocks(d);
+  const TfamStep<TFAM_F_COUNT> plan = tfam_route_layer_fwd(d, bk, layer == 0, true, true, tr_overrides());
+  if (plan.rc) return plan.rc;
+  const int M = bk.M, D = d.D, dh = bk.dh, cpb = bk.cpb, parts = bk.parts, rpb = bk.rpb;
   const float scale = 1.0f / sqrtf((float)dh);
   const vmc_tfam_layer_params& P = layers[layer];
   const TrLayerWs w = tr_lw(ws, d, layer);
@@ -250,25 +50,25 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
     a.M = M; a.N = 3 * D; a.K = D; a.rpb = rpb;
     a.W = (const uint16_t*)P.w_self_in; a.ldw = D; a.bias = P.b_self_in;
     a.out = w.qkv16; a.ldo = 3 * D; a.act = VMC_ACT_NONE;
-    a.frag[0] = ws.qf; a.frag[1] = ws.kf; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = tf_ntt(d.T);
+    a.frag[0] = ws.qf; a.frag[1] = ws.kf; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = bk.ntt_q;
     a.x16out = w.x0_16;
     TfArgs b = {};
     if (d.has_cross) {
       b.A = motion; b.lda = D; b.M = d.B * d.Tk; b.N = 2 * D; b.K = D; b.rpb = 32;
       b.W = (const uint16_t*)P.w_cross_in + (size_t)D * D; b.ldw = D; b.bias = P.b_cross_in + D;
       b.out = w.kv16; b.ldo = 2 * D; b.act = VMC_ACT_NONE;
-      b.frag[0] = ws.kxf; b.frag[1] = nullptr; b.frag_D = D; b.frag_T = d.Tk; b.frag_H = d.H; b.frag_DH = dh; b.frag_NTT = tf_ntt(d.Tk);
+      b.frag[0] = ws.kxf; b.frag[1] = nullptr; b.frag_D = D; b.frag_T = d.Tk; b.frag_H = d.H; b.frag_DH = dh; b.frag_NTT = bk.ntt_kx;
       b.x16out = layer == 0 ? ws.motion16 : nullptr;
     }
     if (layer == 0) {
       a.A = x_in; a.lda = D;
-      rc = d.has_cross ? tr_pair<T, PRO_F32>(a, b, s) : tr_gemm<T, PRO_F32, EPI_ACT16>(a, s);
+      rc = d.has_cross ? tf_run_pair<T, PRO_F32, true>(a, b, plan.p[TFAM_F_QKV], s) : tf_run_single<T, PRO_F32, EPI_ACT16, true>(a, plan.p[TFAM_F_QKV], s);
       resid = x_in;
     } else {
       const TrLayerWs wp = tr_lw(ws, d, layer - 1);
       a.A = wp.y3; a.lda = D; a.eps = 1e-5f; a.ln_g = layers[layer - 1].ln_ffn_g; a.ln_b = layers[layer - 1].ln_ffn_b;
       a.ln_affine = 1; a.xout = w.xin32;
-      rc = d.has_cross ? tr_pair<T, PRO_LN>(a, b, s) : tr_gemm<T, PRO_LN, EPI_ACT16>(a, s);
+      rc = d.has_cross ? tf_run_pair<T, PRO_LN, true>(a, b, plan.p[TFAM_F_QKV], s) : tf_run_single<T, PRO_LN, EPI_ACT16, true>(a, plan.p[TFAM_F_QKV], s);
       resid = w.xin32;
     }
     if (rc) return rc;
@@ -277,13 +77,13 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
     TfArgs a = {};
     a.M = M; a.N = D; a.K = D; a.rpb = rpb; a.cpb = cpb;
     a.q = ws.qf; a.k = ws.kf; a.v = w.qkv16 + 2 * D; a.ldv = 3 * D;
-    a.parts = parts; a.ntt_q = a.ntt_k = tf_ntt(d.T);
+    a.parts = parts; a.ntt_q = a.ntt_k = bk.ntt_q;
     a.kmask = mask; a.T = d.T; a.Tk = d.T; a.H = d.H; a.B = d.B; a.scale = scale;
     a.W = (const uint16_t*)P.w_self_out; a.ldw = D; a.bias = P.b_self_out;
     a.resid = resid; a.ldres = D; a.out = w.y1; a.ldo = D;
     a.lse = w.lse_self; a.oout = w.o_self;
     if (drop) { a.p_attn = p; a.seed_attn = seeds[0]; a.p_drop1 = p; a.seed1 = seeds[1]; a.keep_out = w.keep1; }
-    if ((rc = tr_attn<T>(a, dh, s))) return rc;
+    if ((rc = tf_run_attn<T, true>(a, plan.p[TFAM_F_SELF], s))) return rc;
   }
   const float* yin = w.y1;
   const float *lng = P.ln_self_g, *lnb = P.ln_self_b;
@@ -294,20 +94,20 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
       a.A = w.y1; a.lda = D; a.eps = 1e-5f; a.ln_g = lng; a.ln_b = lnb; a.ln_affine = 1; a.xout = w.x1_32; a.x16out = w.x1_16;
       a.W = (const uint16_t*)P.w_cross_in; a.ldw = D; a.bias = P.b_cross_in;
       a.out = w.q16; a.ldo = D; a.act = VMC_ACT_NONE;
-      a.frag[0] = ws.qf; a.frag[1] = nullptr; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = tf_ntt(d.T);
-      if ((rc = tr_gemm<T, PRO_LN, EPI_ACT16>(a, s))) return rc;
+      a.frag[0] = ws.qf; a.frag[1] = nullptr; a.frag_D = D; a.frag_T = d.T; a.frag_H = d.H; a.frag_DH = dh; a.frag_NTT = bk.ntt_q;
+      if ((rc = tf_run_single<T, PRO_LN, EPI_ACT16, true>(a, plan.p[TFAM_F_Q], s))) return rc;
     }
     {  // F4: y2 = x1 + drop(crossattn(q, K, V) Wo^T + b)
       TfArgs a = {};
       a.M = M; a.N = D; a.K = D; a.rpb = rpb; a.cpb = cpb;
       a.q = ws.qf; a.k = ws.kxf; a.v = w.kv16 + D; a.ldv = 2 * D;
-      a.parts = parts; a.ntt_q = tf_ntt(d.T); a.ntt_k = tf_ntt(d.Tk);
+      a.parts = parts; a.ntt_q = bk.ntt_q; a.ntt_k = bk.ntt_kx;
       a.kmask = mask_kv; a.T = d.T; a.Tk = d.Tk; a.H = d.H; a.B = d.B; a.scale = scale;
       a.W = (const uint16_t*)P.w_cross_out; a.ldw = D; a.bias = P.b_cross_out;
       a.resid = w.x1_32; a.ldres = D; a.out = w.y2; a.ldo = D;
       a.lse = w.lse_cross; a.oout = w.o_cross;
       if (drop) { a.p_attn = p; a.seed_attn = seeds[2]; a.p_drop1 = p; a.seed1 = seeds[3]; a.keep_out = w.keep2; }
-      if ((rc = tr_attn<T>(a, dh, s))) return rc;
+      if ((rc = tf_run_attn<T, true>(a, plan.p[TFAM_F_CROSS], s))) return rc;
     }
     yin = w.y2; lng = P.ln_cross_g; lnb = P.ln_cross_b;
   }
@@ -318,7 +118,7 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
     a.W = (const uint16_t*)P.w_ffn0; a.ldw = D; a.bias = P.b_ffn0;
     a.out = w.h16; a.ldo = d.ff; a.act = VMC_ACT_RELU;
     if (drop) { a.p_drop1 = p; a.seed1 = seeds[4]; }
-    if ((rc = tr_gemm<T, PRO_LN, EPI_ACT16>(a, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_LN, EPI_ACT16, true>(a, plan.p[TFAM_F_FFN0], s))) return rc;
   }
   {  // F6: y3 = x2 + drop(drop(h W2^T + b))
     TfArgs a = {};
@@ -327,26 +127,23 @@ int tr_layer_fwd(const float* x_in, const float* motion, const uint8_t* mask, co
     a.W = (const uint16_t*)P.w_ffn3; a.ldw = d.ff; a.bias = P.b_ffn3;
     a.resid = w.x2_32; a.ldres = D; a.out = w.y3; a.ldo = D;
     if (drop) { a.p_drop1 = p; a.seed1 = seeds[5]; a.p_drop2 = p; a.seed2 = seeds[6]; a.keep_out = w.keep3; }
-    if ((rc = tr_ring<T>(a, s))) return rc;
+    if ((rc = tf_run_ring<T, true>(a, plan.p[TFAM_F_FFN3], s))) return rc;
   }
   return 0;
 }
 
 // ---- head ----------------------------------------------------------------------------------------------------------------
 template <typename T>
-int tr_head_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params& Hd, float* logits, const TrDims& d, const TrWs& ws,
+int tr_head_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params& Hd, float* logits, const TfDims& d, const TrWs& ws,
                 float p_mlp, uint64_t seed, const int* pool_len, hipStream_t s) {
   const int D = d.D;
+  const TfamStep<TFAM_H_COUNT> plan = tfam_route_head_fwd(d, true, tr_overrides());
+  if (plan.rc) return plan.rc;
   const TrLayerWs wl = tr_lw(ws, d, d.L - 1);
   const vmc_tfam_layer_params& PL = layers[d.L - 1];
-  if (D == 768)
-    hipLaunchKernelGGL((tf_pool_kernel<T, 768>), dim3(d.B), dim3(256), 0, s, wl.y3, PL.ln_ffn_g, PL.ln_ffn_b, Hd.cls_ln_g, Hd.cls_ln_b, ws.pool16,
-                       d.T, 1e-5f, pool_len, ws.pooled32);
-  else
-    hipLaunchKernelGGL((tf_pool_kernel<T, 512>), dim3(d.B), dim3(256), 0, s, wl.y3, PL.ln_ffn_g, PL.ln_ffn_b, Hd.cls_ln_g, Hd.cls_ln_b, ws.pool16,
-                       d.T, 1e-5f, pool_len, ws.pooled32);
-  VMC_CHECK_LAUNCH();
   int rc;
+  if ((rc = tf_run_pool<T>(plan.p[TFAM_H_POOL], s, wl.y3, PL.ln_ffn_g, PL.ln_ffn_b, Hd.cls_ln_g, Hd.cls_ln_b, ws.pool16, d.T, pool_len, ws.pooled32)))
+    return rc;
   {
     TfArgs a = {};
     a.M = d.B; a.N = D / 2; a.K = D; a.rpb = 32;
@@ -354,7 +151,7 @@ int tr_head_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params&
     a.W = (const uint16_t*)Hd.w_cls1; a.ldw = D; a.bias = Hd.b_cls1;
     a.out = ws.g16; a.ldo = D / 2; a.act = VMC_ACT_GELU_ERF; a.zout = ws.a16;
     if (p_mlp > 0.f) { a.p_drop1 = p_mlp; a.seed1 = seed; }
-    if ((rc = tr_gemm<T, PRO_16, EPI_ACT16>(a, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_16, EPI_ACT16, true>(a, plan.p[TFAM_H_CLS1], s))) return rc;
   }
   {
     TfArgs a = {};
@@ -362,7 +159,7 @@ int tr_head_fwd(const vmc_tfam_layer_params* layers, const vmc_tfam_head_params&
     a.A = ws.g16; a.lda = D / 2;
     a.W = (const uint16_t*)Hd.w_cls4; a.ldw = D / 2; a.bias = Hd.b_cls4;
     a.out = logits; a.ldo = d.C;
-    if ((rc = tr_gemm<T, PRO_16, EPI_BIAS32>(a, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_16, EPI_BIAS32, true>(a, plan.p[TFAM_H_CLS4], s))) return rc;
   }
   return 0;
 }
@@ -544,30 +341,31 @@ __global__ void __launch_bounds__(256) tr_head_bwd3_kernel(const float* __restri
 }
 
 template <typename T>
-int tr_head_bwd(const float* dlogits, const vmc_tfam_head_params& Hd, const TrDims& d, const TrWs& ws, float p_mlp, uint64_t seed,
+int tr_head_bwd(const float* dlogits, const vmc_tfam_head_params& Hd, const TfDims& d, const TrWs& ws, float p_mlp, uint64_t seed,
                 const int* pool_len, hipStream_t s) {
   const int D = d.D, Dh = D / 2, B = d.B, C = d.C;
+  const TfamStep<3> plan = tfam_route_head_bwd(d);
+  if (plan.rc) return plan.rc;
+  const TfamPlan &p1 = plan.p[0], &p2 = plan.p[1], &p3 = plan.p[2];
   const TrLayerWs wl = tr_lw(ws, d, d.L - 1);
-  const int n1 = Dh / 64 + (C * Dh + C + 511) / 512, n2 = D / 64 + (Dh * D + Dh + 511) / 512;
 #define TR_HB(MB)                                                                                                                             \
   do {                                                                                                                                        \
-    hipLaunchKernelGGL((tr_head_bwd1_kernel<T, MB>), dim3(n1), dim3(512), (512 + MB * C) * sizeof(float), s, dlogits, Hd.w32_cls4, ws.g16,     \
-                       ws.a16, Hd.gw_cls4, Hd.gb_cls4, ws.da, B, C, Dh, p_mlp, seed);                                                         \
-    hipLaunchKernelGGL((tr_head_bwd2_kernel<T, MB>), dim3(n2), dim3(512), (512 + MB * Dh) * sizeof(float), s, ws.da, Hd.w32_cls1, ws.pool16,   \
-                       Hd.gw_cls1, Hd.gb_cls1, ws.dpl, B, Dh, D);                                                                             \
+    hipLaunchKernelGGL((tr_head_bwd1_kernel<T, MB>), dim3(p1.grid), dim3(p1.block), p1.lds, s, dlogits, Hd.w32_cls4, ws.g16, ws.a16,          \
+                       Hd.gw_cls4, Hd.gb_cls4, ws.da, B, C, Dh, p_mlp, seed);                                                                 \
+    hipLaunchKernelGGL((tr_head_bwd2_kernel<T, MB>), dim3(p2.grid), dim3(p2.block), p2.lds, s, ws.da, Hd.w32_cls1, ws.pool16, Hd.gw_cls1,     \
+                       Hd.gb_cls1, ws.dpl, B, Dh, D);                                                                                         \
   } while (0)
-  if ((size_t)32 * C * sizeof(float) > 60 * 1024) return VMC_E_SHAPE;      // the dlogits rows of H1 sit in LDS
-  if (B <= 8) TR_HB(8);
-  else if (B <= 16) TR_HB(16);
+  if (p1.maxb == 8) TR_HB(8);
+  else if (p1.maxb == 16) TR_HB(16);
   else TR_HB(32);
 #undef TR_HB
   VMC_CHECK_LAUNCH();
   if (D == 768)
-    hipLaunchKernelGGL((tr_head_bwd3_kernel<768>), dim3(B + 1), dim3(256), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b, B, d.T,
-                       1e-5f, pool_len);
+    hipLaunchKernelGGL((tr_head_bwd3_kernel<768>), dim3(p3.grid), dim3(p3.block), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b,
+                       B, d.T, 1e-5f, pool_len);
   else
-    hipLaunchKernelGGL((tr_head_bwd3_kernel<512>), dim3(B + 1), dim3(256), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b, B, d.T,
-                       1e-5f, pool_len);
+    hipLaunchKernelGGL((tr_head_bwd3_kernel<512>), dim3(p3.grid), dim3(p3.block), 0, s, ws.pooled32, ws.dpl, Hd.cls_ln_g, wl.dx3, Hd.g_cls_ln_g, Hd.g_cls_ln_b,
+                       B, d.T, 1e-5f, pool_len);
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -587,7 +385,6 @@ struct TrLnProb {
   float* g_gamma;
   float* g_beta;
 };
-constexpr int TR_MAX_PROB = 32, TR_MAX_LN = 12;      // up to four layers' problems in one launch (deferred weight gradients)
 struct TrWgradGroup {
   TrTnProb p[TR_MAX_PROB];
   TrLnProb ln[TR_MAX_LN];
@@ -642,9 +439,9 @@ inline void tr_add_prob(TrWgradGroup& g, const uint16_t* dY, const uint16_t* X, 
   if (g.nprob >= TR_MAX_PROB) { g.nprob = TR_MAX_PROB + 1; return; }      // overflow: reported by tr_wgrad_launch
   TrTnProb& p = g.p[g.nprob++];
   p.dY = dY; p.X = X; p.C = C; p.dbias = dbias; p.M = M; p.N = N; p.K = K; p.lddy = lddy; p.ldx = ldx;
-  p.tiles_k = (K + 127) / 128;
+  p.tiles_k = tfam_tn_tiles_k(K);
   p.tile0 = g.total_tiles;
-  g.total_tiles += ((N + 255) / 256) * p.tiles_k;
+  g.total_tiles += tfam_tn_tiles(N, K);
 }
 inline void tr_add_ln(TrWgradGroup& g, const float* dx, const float* y, const float* stats, float* gg, float* gb) {
   if (gg == nullptr && gb == nullptr) return;
@@ -659,11 +456,12 @@ int tr_wgrad_launch(const TrWgradGroup& g, hipStream_t s) {
   if (blocks == 0) return 0;
   for (int i = 0; i < g.nprob; ++i)
     if (g.p[i].C == nullptr) return VMC_E_ARG;      // a bias gradient without its weight gradient is not a case of this chain
-  const size_t lds = (size_t)TN_STAGES * TN_STAGE;
+  static_assert(TR_WGRAD_LDS == TN_STAGES * TN_STAGE, "tfam_route.h states the TN body's LDS");
+  const size_t lds = TR_WGRAD_LDS;
   auto kern = tr_wgrad_group_kernel<T>;
   static bool attr_done = false;
   if (int rc = set_max_lds(attr_done, (int)TF_LDS_MAX, kern)) return rc;
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(512), lds, s, g);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(TR_WGRAD_NTH), lds, s, g);
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -672,10 +470,12 @@ int tr_wgrad_launch(const TrWgradGroup& g, hipStream_t s) {
 // defer != null: the layer's weight-gradient problems are appended to *defer instead of being launched (vmc_tfam_train_bwd launches
 // all layers' problems once, after the last dgrad chain: one HBM-write-bound launch instead of four with a tail each)
 template <typename T>
-int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, const TrDims& d, const TrWs& ws,
+int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, const TfDims& d, const TrWs& ws,
                  float p, const uint64_t* seeds, int dtype16, hipStream_t s, TrWgradGroup* defer = nullptr) {
-  const int M = d.B * d.T, Mk = d.B * d.Tk, D = d.D, dh = D / d.H;
-  const int rpb = d.T > 32 ? 32 : (d.T <= 16 ? 2 : 1) * d.T;      // the backward's GEMMs are all row-wise: uniform blocks
+  const TfamBlocks bk = tfam_blocks(d);
+  const TfamStep<TFAM_B_COUNT> plan = tfam_route_layer_bwd(d, bk, layer == 0, tr_overrides());
+  if (plan.rc) return plan.rc;
+  const int M = bk.M, Mk = d.B * d.Tk, D = d.D, dh = bk.dh, rpb = bk.rpb;      // the backward's GEMMs are all row-wise: uniform blocks
   const vmc_tfam_layer_params& P = layers[layer];
   const TrLayerWs w = tr_lw(ws, d, layer);
   const bool drop = p > 0.f;
@@ -690,7 +490,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
     a.dyout = w.dy3; a.d16out = w.d3_16; a.stats = w.st3;
     a.W = (const uint16_t*)P.wt_ffn3; a.ldw = D;
     a.out = w.dh16; a.ldo = d.ff; a.act = VMC_ACT_NONE; a.gate = w.h16; a.gate_scale = inv;
-    if ((rc = tr_gemm<T, PRO_LNBWD, EPI_ACT16>(a, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_LNBWD, EPI_ACT16, true>(a, plan.p[TFAM_B_DH], s))) return rc;
   }
   {  // L2: dx2 = dy3 + dh W1
     TfArgs a = {};
@@ -698,7 +498,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
     a.A = w.dh16; a.lda = d.ff;
     a.W = (const uint16_t*)P.wt_ffn0; a.ldw = d.ff;
     a.resid = w.dy3; a.ldres = D; a.out = w.dx2; a.ldo = D;
-    if ((rc = tr_ring<T>(a, s))) return rc;
+    if ((rc = tf_run_ring<T, true>(a, plan.p[TFAM_B_DX2], s))) return rc;
   }
   const float* dx_self = w.dx2;
   if (d.has_cross) {
@@ -710,7 +510,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
       a.dyout = w.dy2; a.d16out = w.d2_16; a.stats = w.st2;
       a.W = (const uint16_t*)P.wt_cross_out; a.ldw = D;
       a.out = w.doc16; a.ldo = D; a.act = VMC_ACT_NONE;
-      if ((rc = tr_gemm<T, PRO_LNBWD, EPI_ACT16>(a, s))) return rc;
+      if ((rc = tf_run_single<T, PRO_LNBWD, EPI_ACT16, true>(a, plan.p[TFAM_B_DOC], s))) return rc;
     }
     // L4: cross-attention backward
     if ((rc = vmc_attention_bwd(w.q16, w.kv16, w.kv16 + D, mask_kv, w.o_cross, w.doc16, w.lse_cross, w.dq16, w.dkv16, w.dkv16 + D, d.B, d.H, d.T,
@@ -722,7 +522,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
       a.A = w.dq16; a.lda = D;
       a.W = (const uint16_t*)P.wt_cross_in; a.ldw = 3 * D;      // columns 0:D of the transposed packed in_proj = Wq^T
       a.resid = w.dy2; a.ldres = D; a.out = w.dx1; a.ldo = D;
-      if ((rc = tr_gemm<T, PRO_16, EPI_RESID32>(a, s))) return rc;
+      if ((rc = tf_run_single<T, PRO_16, EPI_RESID32, true>(a, plan.p[TFAM_B_DX1], s))) return rc;
     }
     dx_self = w.dx1;
   }
@@ -734,7 +534,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
     a.dyout = w.dy1; a.d16out = w.d1_16; a.stats = w.st1;
     a.W = (const uint16_t*)P.wt_self_out; a.ldw = D;
     a.out = w.dos16; a.ldo = D; a.act = VMC_ACT_NONE;
-    if ((rc = tr_gemm<T, PRO_LNBWD, EPI_ACT16>(a, s))) return rc;
+    if ((rc = tf_run_single<T, PRO_LNBWD, EPI_ACT16, true>(a, plan.p[TFAM_B_DOS], s))) return rc;
   }
   // L7: self-attention backward
   if ((rc = vmc_attention_bwd(w.qkv16, w.qkv16 + D, w.qkv16 + 2 * D, mask, w.o_self, w.dos16, w.lse_self, w.dqkv16, w.dqkv16 + D, w.dqkv16 + 2 * D,
@@ -748,7 +548,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
     a.A = w.dqkv16; a.lda = 3 * D;
     a.W = (const uint16_t*)P.wt_self_in; a.ldw = 3 * D;
     a.resid = w.dy1; a.ldres = D; a.out = wp.dx3; a.ldo = D;
-    if ((rc = tr_ring<T>(a, s))) return rc;
+    if ((rc = tf_run_ring<T, true>(a, plan.p[TFAM_B_DX0], s))) return rc;
   }
   // weight, bias and LayerNorm-parameter gradients: one grouped launch
   TrWgradGroup local = {};
@@ -775,21 +575,20 @@ inline bool tr_ws_ok(const void* ws, size_t bytes, const TrWs& w) { return ws !=
 }  // namespace
 
 extern "C" size_t vmc_tfam_train_workspace_bytes(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross) {
-  TrDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
-  if (tr_check(d)) return 0;
-  return tr_ws(nullptr, d).bytes;
+  TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
+  if (tfam_check(d, true)) return 0;
+  return tfam_train_workspace_bytes(d);
 }
 
 extern "C" long long vmc_tfam_train_pool_grad_offset(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross) {
-  TrDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
-  if (tr_check(d)) return -1;
-  const TrWs ws = tr_ws(nullptr, d);
-  return (long long)(uintptr_t)tr_lw(ws, d, L - 1).dx3;      // laid out from a null base: the address is the offset
+  TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};
+  if (tfam_check(d, true)) return -1;
+  return tfam_train_pool_grad_offset(d);
 }
 
 #define TR_PROLOG()                                                         \
-  TrDims d = {B, T, Tk, D, H, ff, L, C, has_cross};                         \
-  if (int rc_ = tr_check(d)) return rc_;                                    \
+  TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross};                         \
+  if (int rc_ = tfam_check(d, true)) return rc_;                            \
   if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;        \
   const TrWs ws = tr_ws(workspace, d);                                      \
   if (!tr_ws_ok(workspace, workspace_bytes, ws)) return VMC_E_ARG;          \
@@ -878,18 +677,16 @@ extern "C" int vmc_tfam_train_bwd_len(const float* dlogits, const uint8_t* mask,
   TR_PROLOG();
   if (!layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
   // the dgrad chains of all layers first, then every weight gradient in ONE launch (the per-layer entry point launches its own).
-  // Four layers' problems fit the table; deeper models flush it every four layers.
+  // TR_WGRAD_FLUSH layers' problems fit the table; deeper models flush it that often (tfam_wgrad_flush).
   TrWgradGroup g = {};
-  int pending = 0;
   for (int l = L - 1; l >= 0; --l) {
     rc = dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, mask_kv, layers, l, d, ws, p_drop, seeds ? seeds + 7 * l : nullptr, dtype16, s, &g)
                              : tr_layer_bwd<F16>(mask, mask_kv, layers, l, d, ws, p_drop, seeds ? seeds + 7 * l : nullptr, dtype16, s, &g);
     if (rc) return rc;
-    if (++pending == 4 || l == 0) {
+    if (tfam_wgrad_flush(L, l)) {
       rc = dtype16 == VMC_BF16 ? tr_wgrad_launch<BF16>(g, s) : tr_wgrad_launch<F16>(g, s);
       if (rc) return rc;
       g = TrWgradGroup{};
-      pending = 0;
     }
   }
   return 0;

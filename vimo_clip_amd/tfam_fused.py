@@ -24,21 +24,28 @@ W_SELF_IN, W_SELF_OUT, W_CROSS_Q, W_CROSS_OUT, W_FFN0, W_FFN3, W_KV_ALL, W_CLS1,
 (P_SELF_IN_B, P_SELF_OUT_B, P_CROSS_Q_B, P_CROSS_OUT_B, P_FFN0_B, P_FFN3_B, P_NORM_SELF, P_NORM_CROSS, P_NORM_FFN,
  P_KV_ALL_B, P_CLS_LN, P_CLS1_B, P_CLS4_B, P_END) = range(16, 30)
 
-MAX_T = 64        # tokens per clip (TF_MAX_T of csrc/tfam_kernels.h): queries in parts of 32 per row block, up to four key tiles
 MAX_ROWS = 256      # B*T above which the per-op path (256x256 GEMM tiles) wins: measured crossover B = 16 at T = 16 (profiles/README.md)
 
 
-def supported(model, B, T, Tk, has_cross) -> bool:
-    """Shapes the fused chain covers (everything else takes the per-op path)."""
-    D, H = model.d_model, model.nhead
-    ff = model.layers[0].ffn[0].weight.shape[0]
-    if D not in (512, 768) or D % H or D // H not in (64, 96):
+def dims(model, B, T, Tk, has_cross):
+    """(B, T, Tk, D, H, ff, L, C, has_cross) as the vmc_tfam_* entries take them."""
+    return (B, T, Tk, model.d_model, model.nhead, model.layers[0].ffn[0].weight.shape[0], len(model.layers),
+            model.classifier[4].weight.shape[0], int(has_cross))
+
+
+def supported(model, B, T, Tk, has_cross, train=False) -> bool:
+    """Batches that take the fused chain (everything else takes the per-op path): the shapes the library accepts
+    (vmc_tfam_supported), below the measured crossover, on a model with the ReLU feed-forward the chain computes."""
+    if B * T > MAX_ROWS or model.layers[0].ffn_act != 3:      # ReLU (ops.ACT_RELU): what the reference always runs (:13,81)
         return False
-    if not 0 < T <= MAX_T or (has_cross and not 0 < Tk <= MAX_T) or ff % 512 or B * T > MAX_ROWS:
-        return False
-    if ((2 if T <= 16 else 1) * H) % 4:
-        return False
-    return model.layers[0].ffn_act == 3      # ReLU (ops.ACT_RELU): what the reference always runs (:13,81)
+    key = dims(model, B, T, Tk, has_cross) + (int(train),)
+    ok = _answers.get(key)
+    if ok is None:
+        ok = _answers[key] = lib.vmc_tfam_supported(*key) == 0
+    return ok
+
+
+_answers = {}      # vmc_tfam_supported is a pure function of its arguments: asked once per shape, not once per forward
 
 
 class TfamPack:

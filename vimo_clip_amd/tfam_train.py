@@ -43,12 +43,9 @@ SEEDS_PER_LAYER = 7
 
 
 def supported(model, B, T, Tk, has_cross) -> bool:
-    """Shapes the training chain covers: the eval chain's set, at most 256 token rows (the grouped weight gradient keeps the
-    whole contraction in four LDS stages), at most 32 clips, a class count that is a multiple of 4."""
-    if not tfam_fused.supported(model, B, T, Tk, has_cross):
-        return False
-    C = model.classifier[4].weight.shape[0]
-    return B * T <= 256 and (not has_cross or B * Tk <= 256) and B <= 32 and C % 4 == 0
+    """Batches that take the training chains: tfam_fused.supported's policy over the shapes vmc_tfam_supported accepts for training
+    (the eval chain's set, at most 256 token rows, at most 32 clips, a class count that is a multiple of 4 and at most 480)."""
+    return tfam_fused.supported(model, B, T, Tk, has_cross, train=True)
 
 
 def _grad_dst(p, fresh):
@@ -172,11 +169,6 @@ def _tables(model, dtype16, cross) -> _Tables:
     return t
 
 
-def _dims(model, B, T, Tk, cross):
-    D, H, L = model.d_model, model.nhead, len(model.layers)
-    return (B, T, Tk, D, H, model.layers[0].ffn[0].weight.shape[0], L, model.classifier[4].weight.shape[0], int(cross))
-
-
 class TfamTrainFn(torch.autograd.Function):
     """logits = AMO_CLIP(x, motion) in train mode.  Inputs after ``seeds`` are the parameters (so that autograd asks for their
     gradients); their values are read through the pointer tables, not through these tensors."""
@@ -186,7 +178,7 @@ class TfamTrainFn(torch.autograd.Function):
         dt16 = model.compute_dtype
         B, T, D = x.shape
         Tk = motion.shape[1] if cross else 0
-        dims = _dims(model, B, T, Tk, cross)
+        dims = tfam_fused.dims(model, B, T, Tk, cross)
         tab = _tables(model, dt16, cross)
         layers, head = tab.build()
         nbytes = lib.vmc_tfam_train_workspace_bytes(*dims)
