@@ -74,6 +74,42 @@ int vmc_patches_u8_exact(const uint8_t* frames, void* patches, int F, int R, int
                          void* stream);
 int vmc_patches_f32_split(const float* pixel_values, void* patches, int F, int R, int p, int kpad, int dtype16, void* stream);
 
+/* Grey twins of vmc_preprocess_patches_u8 / vmc_patches_u8_exact for frames whose three channels are one plane (frame-difference
+ * motion frames, vmc_frame_diff_gray_u8 below):  frames u8 [F,1,R,R], every other argument as the original.  `patches` receives the
+ * bytes the original writes when given that plane three times (wrap_quirk, zeroed pad columns, bf16 / f16, even and odd p alike);
+ * a third of the bytes are read.  The patch GEMM keeps its 3 p^2-deep K: folding the channels would change the sums' bits. */
+int vmc_preprocess_patches_gray_u8(const uint8_t* frames, void* patches, int F, int R, int p, int kpad,
+                                   int wrap_quirk, int dtype16, void* stream);
+int vmc_patches_gray_u8_exact(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk, int dtype16,
+                              void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Frame-difference motion frames from RGB frames.
+ * Replaces the host loop  cv2.cvtColor(frame, COLOR_BGR2GRAY) -> cv2.absdiff(curr, prev)  of
+ * utils/generate_frame_diff_video.py:37-54 (the arithmetic before its lossy H.264 encode), whose output every *_frame_diff*
+ * twin consumes as three identical channels.
+ *   frames  u8, T RGB frames of H x W addressed by BYTE strides: element (t, c, y, x) at
+ *           frames + t*stride_t + c*stride_c + y*stride_y + x*stride_x.  [T,H,W,3] (decoders), [T,3,H,W]
+ *           (FlowStudentModel.forward) and permuted / sliced views of either need no copy.
+ *   prev    NULL, or ONE frame that precedes frames[0] with the same stride_c / stride_y / stride_x (the previous chunk's
+ *           last frame when a video is streamed in chunks)
+ *   n_out   = T - 1 + (prev != NULL)
+ *   gray(p) = (w_r*R + w_g*G + w_b*B + (1 << (shift-1))) >> shift
+ *   out     u8 [n_out, channels_out, H, W] planar, contiguous:  out[t] = |gray(f[t+1]) - gray(f[t])|, f = (prev,) frames[0..T-1];
+ *           channels_out is 1 or 3 (the plane is written three times)
+ * Weights: 9798, 19235, 3735, shift 15 = OpenCV 4.x 8-bit COLOR_BGR2GRAY (parity unpinned: cv2 is absent here);
+ * 4899, 9617, 1868, shift 14 = the 14-bit constants of other OpenCV builds.
+ * VMC_E_ARG, before any launch: frames or out NULL, T / H / W <= 0, n_out <= 0, channels_out not 1 or 3, shift outside 1..22,
+ * a negative weight, w_r + w_g + w_b != 1 << shift (the sum rule keeps gray <= 255).
+ * HBM: 3 B read + channels_out B written per output pixel; 4-byte accesses per lane where 4 whole pixels sit at a 4-byte
+ * aligned address (stride_x == 3 with stride_c == 1, or stride_x == 1), bytes elsewhere, the same result either way.  A thread
+ * walks time and keeps the previous frame's grey values in registers; the outputs are split into time segments of at least
+ * VMC_FRAME_DIFF_MIN_SEG frames only as far as the grid needs to fill the machine (csrc/frame_diff.hip). */
+#define VMC_FRAME_DIFF_MIN_SEG 8
+int vmc_frame_diff_gray_u8(const uint8_t* frames, const uint8_t* prev, uint8_t* out, int T, int H, int W,
+                           long long stride_t, long long stride_c, long long stride_y, long long stride_x,
+                           int w_r, int w_g, int w_b, int shift, int channels_out, void* stream);
+
 /* Pillow-exact antialiased resample of planar u8 images [planes, in_h, in_w] along one axis — the BICUBIC
  * ``Resize`` of clip._transform (models/student_model.py:77-78) and of CLIPImageProcessor (extract_embeddings.py:91),
  * both of which call PIL.Image.resize.  out pixel o (of the resampled axis) = clip8((2^21 + sum_t in[lo_o + t] *

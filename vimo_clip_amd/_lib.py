@@ -28,6 +28,9 @@ SIGNATURES = {
     "vmc_patches_f32": (I, [P, P, I, I, I, I, I, P]),
     "vmc_patches_u8_exact": (I, [P, P, I, I, I, I, I, I, P]),
     "vmc_patches_f32_split": (I, [P, P, I, I, I, I, I, P]),
+    "vmc_preprocess_patches_gray_u8": (I, [P, P, I, I, I, I, I, I, P]),
+    "vmc_patches_gray_u8_exact": (I, [P, P, I, I, I, I, I, I, P]),
+    "vmc_frame_diff_gray_u8": (I, [P, P, P, I, I, I] + [ctypes.c_longlong] * 4 + [I, I, I, I, I, P]),
     "vmc_resample_u8": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "vmc_linear": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, I, I, I, I, P]),
     "vmc_linear_preact": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, I, I, I, I, I, P]),

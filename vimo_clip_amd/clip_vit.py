@@ -337,6 +337,23 @@ class VisionTransformer(nn.Module):
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     @torch.no_grad()
+    def encode_gray_u8(self, gray_u8: torch.Tensor, wrap_quirk: bool = False, crop_mode: str = "torchvision") -> torch.Tensor:
+        """[F,1,H,W] u8 -> [F,E] f32: ``encode_frames_u8`` of the plane repeated three times, bit for bit, with one plane through
+        resize / crop and a third of the bytes read by patch extraction (frame-difference motion frames, ops.frame_diff_gray)."""
+        if gray_u8.dim() != 4 or gray_u8.shape[1] != 1 or gray_u8.dtype != torch.uint8:
+            raise ValueError("gray frames must be u8 [F,1,H,W]")
+        outs = []
+        for s in range(0, gray_u8.shape[0], self.frame_chunk):
+            fr, wrap = self.fit_frames_u8(gray_u8[s:s + self.frame_chunk], wrap_quirk, crop_mode)
+            if self.exact_patch_embed:
+                patches = ops.patches_gray_u8_exact(fr, self.patch_size, self.compute_dtype, wrap)
+                outs.append(self._encode_patches(patches, fr.shape[0], patch_mode="u8_exact"))
+            else:
+                patches = ops.preprocess_patches_gray_u8(fr, self.patch_size, self.compute_dtype, wrap)
+                outs.append(self._encode_patches(patches, fr.shape[0]))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    @torch.no_grad()
     def encode_pixel_values(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """[F,3,R,R] normalised floats -> [F,E] f32 (the ``visual_encoder(x)`` call of student_model.py:84)."""
         outs = []

@@ -78,6 +78,62 @@ extern "C" int vmc_preprocess_patches_u8(const uint8_t* frames, void* patches, i
   return 0;
 }
 
+// Grey frames u8 [F,1,R,R] -> the patch matrix vmc_preprocess_patches_u8 writes for the same plane given three times: a thread
+// reads its 4 pixels once and writes them into the three channel slices of the patch row (a third of the bytes read).
+template <typename T>
+__global__ void __launch_bounds__(256) preprocess_gray_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
+                                                              int F, int R, int p, int kpad, int wrap) {
+  const int g = R / p;
+  const int quads_per_row = R >> 2;
+  const size_t total = (size_t)F * R * quads_per_row;
+  const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
+  const float istd[3] = {1.0f / 0.26862954f, 1.0f / 0.26130258f, 1.0f / 0.27577711f};
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xq = (int)(i % quads_per_row);
+    const size_t t = i / quads_per_row;
+    const int y = (int)(t % R);
+    const int f = (int)(t / R);
+    const uint32_t px = *(const uint32_t*)(frames + i * 4);
+    const int py = y / p, dy = y % p;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = xq * 4 + j;
+      uint32_t v = (px >> (8 * j)) & 0xFFu;
+      if (wrap) v = (256u - v) & 0xFFu;
+      const int pxi = x / p, dx = x % p;
+      const size_t prow = ((size_t)f * g + py) * g + pxi;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const float val = ((float)v / 255.0f - mean[c]) * istd[c];      // the expression of preprocess_kernel
+        patches[prow * kpad + (c * p + dy) * p + dx] = T::from_f32(val);
+      }
+    }
+  }
+}
+
+extern "C" int vmc_preprocess_patches_gray_u8(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk,
+                                              int dtype16, void* stream) {
+  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
+  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
+  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
+  const size_t total = (size_t)F * R * (R / 4);
+  hipStream_t s = (hipStream_t)stream;
+  const int k = 3 * p * p;
+  if (kpad > k) {
+    const size_t rows = (size_t)F * (R / p) * (R / p);
+    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
+    VMC_CHECK_LAUNCH();
+  }
+  if (dtype16 == VMC_BF16)
+    hipLaunchKernelGGL(preprocess_gray_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
+  else if (dtype16 == VMC_F16)
+    hipLaunchKernelGGL(preprocess_gray_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
+  else
+    return VMC_E_DTYPE;
+  VMC_CHECK_LAUNCH();
+  return 0;
+}
+
 // Same patch extraction for frames that are already normalised floats (HF `pixel_values`, the
 // argument of CLIPModel.get_image_features at extract_embeddings.py:94).
 template <typename T>
@@ -237,6 +293,79 @@ extern "C" int vmc_patches_u8_exact(const uint8_t* frames, void* patches, int F,
     hipLaunchKernelGGL(patches_u8_exact_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
   else if (dtype16 == VMC_F16)
     hipLaunchKernelGGL(patches_u8_exact_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
+  else
+    return VMC_E_DTYPE;
+  VMC_CHECK_LAUNCH();
+  return 0;
+}
+
+// vmc_patches_u8_exact for grey frames u8 [F,1,R,R]: the bytes it writes for the same plane given three times.
+template <typename T>
+__global__ void __launch_bounds__(256) patches_gray_u8_exact_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
+                                                                    int F, int R, int p, int kpad, int wrap) {
+  const int g = R / p;
+  const int quads_per_row = R >> 2;
+  const size_t total = (size_t)F * R * quads_per_row;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xq = (int)(i % quads_per_row);
+    const size_t t = i / quads_per_row;
+    const int y = (int)(t % R);
+    const int f = (int)(t / R);
+    const uint32_t px = *(const uint32_t*)(frames + i * 4);
+    const int py = y / p, dy = y % p;
+    if ((p & 1) == 0) {        // even patch size: pixel pairs never straddle a patch -> 4-byte stores (as patches_u8_exact_kernel)
+#pragma unroll
+      for (int j = 0; j < 4; j += 2) {
+        const int x = xq * 4 + j;
+        uint32_t v0 = (px >> (8 * j)) & 0xFFu, v1 = (px >> (8 * j + 8)) & 0xFFu;
+        if (wrap) { v0 = (256u - v0) & 0xFFu; v1 = (256u - v1) & 0xFFu; }
+        const int pxi = x / p, dx = x % p;
+        const size_t prow = ((size_t)f * g + py) * g + pxi;
+        const uint32_t h2 = (uint32_t)T::from_f32((float)v0) | ((uint32_t)T::from_f32((float)v1) << 16);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
+          *(uint32_t*)dst = h2;
+          *(uint32_t*)(dst + kpad) = h2;
+        }
+      }
+      continue;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int x = xq * 4 + j;
+      uint32_t v = (px >> (8 * j)) & 0xFFu;
+      if (wrap) v = (256u - v) & 0xFFu;
+      const int pxi = x / p, dx = x % p;
+      const size_t prow = ((size_t)f * g + py) * g + pxi;
+      const uint16_t h = T::from_f32((float)v);              // integers <= 255 are exact in bf16 and f16
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
+        dst[0] = h;
+        dst[kpad] = h;
+      }
+    }
+  }
+}
+
+extern "C" int vmc_patches_gray_u8_exact(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk, int dtype16,
+                                         void* stream) {
+  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
+  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
+  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
+  const size_t total = (size_t)F * R * (R / 4);
+  hipStream_t s = (hipStream_t)stream;
+  const int k = 3 * p * p;
+  if (kpad > k) {
+    const size_t rows = (size_t)F * (R / p) * (R / p);
+    hipLaunchKernelGGL(zero_pad_cols_multi_kernel, dim3(grid_for(rows * (kpad - k) * 2, 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad, 2);
+    VMC_CHECK_LAUNCH();
+  }
+  if (dtype16 == VMC_BF16)
+    hipLaunchKernelGGL(patches_gray_u8_exact_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
+  else if (dtype16 == VMC_F16)
+    hipLaunchKernelGGL(patches_gray_u8_exact_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
   else
     return VMC_E_DTYPE;
   VMC_CHECK_LAUNCH();

@@ -80,16 +80,27 @@ class _Committer:
 
 @torch.no_grad()
 def process_and_write_video_incremental(video_path, model, h5f, chunk_size=256, min_free_gb=0.0, compression="lzf",
-                                        frame_source=None, commit=None):
-    """inference_frame_diff.py:235-312.  Returns the final ``(T, D)`` shape."""
+                                        frame_source=None, commit=None, motion_from_rgb=False):
+    """inference_frame_diff.py:235-312.  Returns the final ``(T, D)`` shape.
+    ``motion_from_rgb``: ``video_path`` is an RGB video; every chunk is turned into frame-difference motion frames on the device
+    (``model.forward_from_rgb``), the previous chunk's last frame carried over as one device frame, so a video of ``T`` frames
+    gives ``T - 1`` rows whatever the chunk size; a one-frame video takes the empty-video branch."""
     video_id = os.path.splitext(os.path.basename(video_path))[0]
     group = h5f.require_group(video_id)
     if "embeddings" in group:
         return tuple(group["embeddings"].shape)
     commit = commit or (lambda force=False: h5f.flush())
-    dset, embed_dim, total = None, None, 0
+    dset, embed_dim, total, prev = None, None, 0, None
     for frames in iter_frame_chunks(video_path, chunk_size, min_free_gb, frame_source):
-        out, _, _ = model(frames.unsqueeze(0))                                  # (1, n, D)
+        if motion_from_rgb:
+            rgb = frames.unsqueeze(0).to(model.device)
+            if prev is None and rgb.shape[1] < 2:                               # nothing to difference yet
+                prev = rgb[:, -1].clone()
+                continue
+            out, _, _ = model.forward_from_rgb(rgb, prev=prev)                  # (1, n - 1 + (prev given), D)
+            prev = rgb[:, -1].clone()
+        else:
+            out, _, _ = model(frames.unsqueeze(0))                              # (1, n, D)
         emb = out.squeeze(0).float().cpu().numpy().astype("float32")
         if embed_dim is None:
             embed_dim = emb.shape[1]
@@ -111,9 +122,10 @@ def process_and_write_video_incremental(video_path, model, h5f, chunk_size=256, 
 
 @torch.no_grad()
 def export_embeddings(video_paths, model, output_h5_path, resume=False, overwrite=False, chunk_size=256, min_free_gb=0.0,
-                      compression="lzf", frame_source=None, flush_interval_s=5.0, streaming=True):
+                      compression="lzf", frame_source=None, flush_interval_s=5.0, streaming=True, motion_from_rgb=False):
     """Main loop of inference_frame_diff.py:318-410 (``streaming=True``) or inference.py:94-114 (``streaming=False``: the
     whole video in one forward, plain contiguous ``embeddings`` dataset, file rewritten from scratch).
+    ``motion_from_rgb``: the paths are RGB videos and the motion frames are computed on the device (``T - 1`` rows per video).
     Returns ``{"processed", "skipped_existing", "skipped_low_ram", "errors"}``."""
     model.eval()
     out_dir = os.path.dirname(output_h5_path)
@@ -129,7 +141,7 @@ def export_embeddings(video_paths, model, output_h5_path, resume=False, overwrit
                 video_id = os.path.splitext(os.path.basename(video_path))[0]
                 vr = (frame_source or open_video)(video_path)
                 frames = vr.get_batch(np.arange(len(vr))).permute(0, 3, 1, 2)
-                emb, _, _ = model(frames.unsqueeze(0))
+                emb, _, _ = model.forward_from_rgb(frames.unsqueeze(0)) if motion_from_rgb else model(frames.unsqueeze(0))
                 h5f.create_group(video_id).create_dataset("embeddings", data=emb.squeeze(0).float().cpu().numpy())
                 stats["processed"] += 1
         return stats
@@ -144,7 +156,8 @@ def export_embeddings(video_paths, model, output_h5_path, resume=False, overwrit
                 stats["skipped_existing"] += 1
                 continue
             try:
-                process_and_write_video_incremental(video_path, model, h5f, chunk_size, min_free_gb, compression, frame_source, commit)
+                process_and_write_video_incremental(video_path, model, h5f, chunk_size, min_free_gb, compression, frame_source, commit,
+                                                    motion_from_rgb)
                 stats["processed"] += 1
             except LowMemoryError as e:
                 warnings.warn(f"Skipping {video_id} due to low RAM: {e}")

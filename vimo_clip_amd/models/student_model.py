@@ -101,9 +101,15 @@ class FlowStudentModel(nn.Module):
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if train:
             emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=True)          # [B*T, E] f32
-            e_out, e_mlp, e_pool = _fork3(emb, self.compute_dtype)
         else:
             emb = self.visual_encoder.encode_frames_u8(frames, wrap_quirk=True)
+        return self._heads(emb, train, B, T)
+
+    def _heads(self, emb, train, B, T):
+        """Frame embeddings [B*T, E] -> the three outputs of forward (residual MLP, mean pool, classification head)."""
+        if train:
+            e_out, e_mlp, e_pool = _fork3(emb, self.compute_dtype)
+        else:
             e_out = e_mlp = e_pool = emb
         E = emb.shape[-1]
         emb_distill = self.residual_mlp(e_mlp.view(B, T, E))
@@ -111,6 +117,32 @@ class FlowStudentModel(nn.Module):
         h = ag.linear(pooled, self.classification_head[0].weight, self.classification_head[0].bias, act=ops.ACT_RELU)
         logits = ag.linear(h, self.classification_head[2].weight, self.classification_head[2].bias, out_f32=True)
         return e_out.view(B, T, E), emb_distill, logits
+
+    def forward_from_rgb(self, rgb_videos, prev=None):
+        """rgb_videos [B,T,3,H,W] u8 -> (embeddings [B,T-1,E], embeddings_for_distillation [B,T-1,E], logits [B,C]): the motion
+        frames |gray(f[t+1]) - gray(f[t])| are computed on the device (ops.frame_diff_gray: the arithmetic of the reference's
+        utils/generate_frame_diff_video.py before its lossy encode) and fed to the student, so T teacher frames pair with T-1 motion
+        frames (train.py:98).  Differences are taken inside a clip, never across clips.  ``prev`` [B,3,H,W] u8: one frame per clip
+        that precedes it (a clip continued from an earlier chunk); every clip then yields T motion frames.
+        Without gradients the grey plane goes through resize, crop and patch extraction once (encode_gray_u8); with gradients the
+        three-channel differences are materialised and ``forward`` runs unchanged.  Same result either way."""
+        if rgb_videos.dim() != 5 or rgb_videos.shape[2] != 3 or rgb_videos.dtype != torch.uint8:
+            raise ValueError("rgb_videos must be u8 [B,T,3,H,W]")
+        B, T, _, H, W = rgb_videos.shape
+        n = T - 1 + (prev is not None)
+        if n <= 0:
+            raise ValueError("forward_from_rgb needs two frames per clip (or one and `prev`)")
+        rgb = rgb_videos.to(self.device)
+        prev = prev.to(self.device) if prev is not None else None
+        train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        ch = 3 if train else 1
+        diff = torch.empty((B, n, ch, H, W), dtype=torch.uint8, device=rgb.device)
+        for b in range(B):
+            ops.frame_diff_gray(rgb[b], prev[b] if prev is not None else None, channels=ch, out=diff[b])
+        if train:
+            return self.forward(diff)
+        emb = self.visual_encoder.encode_gray_u8(diff.view(B * n, 1, H, W), wrap_quirk=True)
+        return self._heads(emb, False, B, n)
 
 
 def _fork3(x, dt16):

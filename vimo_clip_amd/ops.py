@@ -254,6 +254,88 @@ def patches_u8_exact(frames_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: b
     return out
 
 
+def preprocess_patches_gray_u8(gray_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
+    """preprocess_patches_u8 of the plane given three times, read once (vmc_preprocess_patches_gray_u8).  gray_u8: u8 [F,1,R,R]."""
+    F, C, R, R2 = gray_u8.shape
+    if C != 1 or R != R2 or gray_u8.dtype != torch.uint8:
+        raise ValueError("frames must be u8 [F,1,R,R]")
+    gray_u8 = gray_u8.contiguous()
+    g = R // patch
+    kpad = _kpad(3 * patch * patch)
+    out = torch.empty((F * g * g, kpad), dtype=dtype16, device=gray_u8.device)
+    check(lib.vmc_preprocess_patches_gray_u8(ptr(gray_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()),
+          "preprocess_patches_gray_u8")
+    return out
+
+
+def patches_gray_u8_exact(gray_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
+    """patches_u8_exact of the plane given three times, read once (vmc_patches_gray_u8_exact).  gray_u8: u8 [F,1,R,R]."""
+    F, C, R, R2 = gray_u8.shape
+    if C != 1 or R != R2 or gray_u8.dtype != torch.uint8:
+        raise ValueError("frames must be u8 [F,1,R,R]")
+    gray_u8 = gray_u8.contiguous()
+    g = R // patch
+    kpad = _kpad(3 * patch * patch)
+    out = torch.empty((F * g * g, 2 * kpad), dtype=dtype16, device=gray_u8.device)
+    check(lib.vmc_patches_gray_u8_exact(ptr(gray_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()),
+          "patches_gray_u8_exact")
+    return out
+
+
+GRAY_WEIGHTS_CV8 = (9798, 19235, 3735, 15)      # OpenCV 4.x 8-bit COLOR_BGR2GRAY: R, G, B weights and the shift
+GRAY_WEIGHTS_14BIT = (4899, 9617, 1868, 14)     # the 14-bit constants of other OpenCV builds
+FRAME_DIFF_MIN_SEG = 8                          # VMC_FRAME_DIFF_MIN_SEG (include/vmc.h): shortest time segment of the kernel
+
+
+def frame_diff_gray(frames: torch.Tensor, prev: torch.Tensor = None, channels: int = 1, weights=GRAY_WEIGHTS_CV8,
+                    layout: str = "nchw", out: torch.Tensor = None) -> torch.Tensor:
+    """Frame-difference motion frames |gray(f[t+1]) - gray(f[t])| of RGB frames (vmc_frame_diff_gray_u8), the arithmetic of the
+    reference's utils/generate_frame_diff_video.py before its lossy encode.
+    frames: u8 device tensor, [T,3,H,W] (layout="nchw") or [T,H,W,3] (layout="nhwc"), any strides (views are read in place).
+    prev:   one frame [3,H,W] / [H,W,3] that precedes frames[0] (the previous chunk's last frame), or None.
+    Returns u8 [n_out, channels, H, W], n_out = T - 1 + (prev is not None); empty when n_out == 0.
+    out:    optional contiguous u8 device tensor of that shape to write into (e.g. one clip's slice of a batch)."""
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError("layout must be 'nchw' or 'nhwc'")
+    if frames.dtype != torch.uint8 or frames.dim() != 4:
+        raise ValueError("frames must be a 4-D u8 tensor")
+    if layout == "nhwc":
+        frames = frames.permute(0, 3, 1, 2)
+        if prev is not None:
+            prev = prev.permute(2, 0, 1)
+    T, C, H, W = frames.shape
+    if C != 3:
+        raise ValueError(f"frames must have 3 channels, got {C} (layout={layout!r})")
+    if channels not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    if prev is not None:
+        if prev.dtype != torch.uint8 or tuple(prev.shape) != (3, H, W) or prev.device != frames.device:
+            raise ValueError("prev must be one u8 frame of the frames' shape, layout and device")
+        if prev.stride() != frames.stride()[1:]:
+            prev = _restride_like(prev, frames)
+    n_out = T - 1 + (prev is not None)
+    shape = (max(n_out, 0), channels, H, W)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frames.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError(f"out must be a contiguous u8 tensor of shape {shape} on the frames' device")
+    if n_out <= 0 or H == 0 or W == 0:
+        return out
+    w_r, w_g, w_b, shift = (int(v) for v in weights)
+    st, sc, sy, sx = frames.stride()
+    check(lib.vmc_frame_diff_gray_u8(ptr(frames), ptr(prev), ptr(out), T, H, W, st, sc, sy, sx, w_r, w_g, w_b, shift, channels, stream()),
+          "frame_diff_gray_u8")
+    return out
+
+
+def _restride_like(prev: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
+    """One-frame copy of prev [3,H,W] with the channel / row / pixel strides of frames [T,3,H,W] (the kernel addresses both with one
+    stride triple).  Memory plumbing: a single frame."""
+    buf = torch.empty_strided(prev.shape, frames.stride()[1:], dtype=prev.dtype, device=prev.device)
+    buf.copy_(prev)
+    return buf
+
+
 def patches_f32_split(pixel_values: torch.Tensor, patch: int, dtype16) -> torch.Tensor:
     """[F*g*g, 3*kpad] = [x_hi | x_lo | x_hi] (vmc_patches_f32_split)."""
     F, C, R, R2 = pixel_values.shape

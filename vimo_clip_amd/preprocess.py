@@ -74,7 +74,7 @@ def center_crop_offsets(h: int, w: int, n_px: int, mode: str = "torchvision"):
 
 
 def resize_center_crop_u8(frames: torch.Tensor, n_px: int, crop_mode: str = "torchvision", wrap_quirk: bool = False) -> torch.Tensor:
-    """[F,3,H,W] u8 -> [F,3,n_px,n_px] u8 = CenterCrop(n_px)(Resize(n_px, BICUBIC)(frame)), PIL-exact.
+    """[F,C,H,W] u8 (any channel count) -> [F,C,n_px,n_px] u8 = CenterCrop(n_px)(Resize(n_px, BICUBIC)(frame)), PIL-exact.
     ``wrap_quirk`` first maps every input pixel v -> (256 - v) mod 256."""
     if frames.dtype != torch.uint8 or frames.dim() != 4:
         raise ValueError("frames must be u8 [F,C,H,W]")
