@@ -3,7 +3,7 @@
  *
  * The reference (MarcosRodrigoT/VIMO-CLIP) has no FFI: its hot path sits behind Python nn.Module /
  * function signatures and runs on stock PyTorch ATen ops.  Each entry point below replaces the ATen
- * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16).
+ * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17 is this project's own).
  * The Python mirror of the reference interface (vimo_clip_amd/) calls these through ctypes.
  *
  * Conventions
@@ -614,6 +614,35 @@ int vmc_grad_clip_dev(const float* grad, size_t n, float* hyper, float* clip, vo
                       void* stream);
 /* sum of squares of a flat f32 buffer, accumulated (+=) into out[0] (global grad norm). */
 int vmc_sumsq(const float* x, size_t n, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K17 — batch assembly from a device-resident embedding store: HDF5VideoDataset.__getitem__ + collate_fn_pad
+ * (TFAM/data/dataset.py:38-51, 76-112) for videos whose rows already sit in device memory.
+ *   One launch assembles every stream's padded tokens and mask, the label rows and the max_len values.  The copy is exact (fp32 in,
+ *   fp32 out) and EVERY output element is written on every call, padding rows included: a graph replay never sees the bytes of the
+ *   previous batch.  16-byte accesses where D % 4 == 0 and `rows` and `out` are 16-byte aligned, 4-byte accesses otherwise (neither
+ *   is an error).  `streams` is a HOST array read at enqueue time (as vmc_tfam_layer_params is); everything it points to, `index`,
+ *   `labels`, `labels_out` and `status` are device memory.  The call only enqueues: no synchronisation, safe under capture.
+ *   max_len: the "POOL LENGTH" value of the assembled batch (above), max over b of min(length, T_out), at least 1, written by one
+ *   thread that loops over the B indices (no atomics: the same bits on every replay).
+ *   status: sticky, *status |= bits, written by that thread.  Bit 1: an index outside [0, n_videos); bit 2: a clip longer than
+ *   T_out was truncated.  The host zeroes it and reads it when it likes (once per epoch, say).
+ *   The kernel checks every index BEFORE it forms an address from it (the host cannot validate device memory): an index out of
+ *   range gives an empty clip -- zero rows, zero mask, zero label row.  A negative length counts as 0.
+ * VMC_E_ARG, before any launch: streams / rows / offset / length / out / mask / index NULL, labels_out NULL or C <= 0 while labels
+ * is given, B / D / T_out / n_videos <= 0, n_streams outside 1..2.  VMC_E_SHAPE: B > 65535. */
+typedef struct vmc_clip_stream {
+  const float* rows;        /* [total_rows, D] fp32, the videos' rows back to back */
+  const long long* offset;  /* [n_videos] first row of video i */
+  const int* length;        /* [n_videos] rows of video i; 0 is allowed */
+  float* out;               /* [B, T_out, D]; rows t >= length are written as zeros */
+  uint8_t* mask;            /* [B, T_out]; 1 = real token (arange(T) < length) */
+  int* max_len;             /* one int32 in device memory, may be NULL: max over b of min(length, T_out), at least 1 */
+  int T_out;
+} vmc_clip_stream;
+int vmc_gather_clips(const vmc_clip_stream* streams, int n_streams /* 1 or 2 */, const int* index /* device, [B] */, int B,
+                     long long n_videos, int D, const float* labels /* [n_videos, C] or NULL */, float* labels_out /* [B, C] */,
+                     int C, int* status /* device, one int32, may be NULL */, void* stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ class Config:
         self.task, self.motion_key, self.use_graphs = "multilabel", "flow", False    # use_graphs: hipGraph replay of the eval forward
         self.graph_bucket = 1      # use_graphs with ragged loaders: pad clip lengths to multiples of this, one graph per bucket (graphs.pad_to_bucket)
         self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
+        self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
 
@@ -67,6 +68,8 @@ class Config:
             kw["graph_bucket"] = int(t["graph_bucket"])
         if t.get("grad_clip_norm") is not None:     # optional as well
             kw["grad_clip_norm"] = float(t["grad_clip_norm"])
+        if "device_store" in t:                     # optional as well
+            kw["device_store"] = bool(t["device_store"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -94,6 +97,28 @@ def batches(dataset, batch_size, rank=0, world=1, drop_last=True, order=None, mo
     idx = idx[lo:hi]
     for s in range(0, len(idx) - (batch_size - 1 if drop_last else 0), batch_size):
         yield collate_fn_pad([dataset[i] for i in idx[s:s + batch_size]], motion_key=motion_key)
+
+
+def index_batches(n, batch_size, rank=0, world=1, drop_last=True, order=None):
+    """The index lists of ``batches()`` without the items: (pos, ids) with ``ids`` the batch's dataset indices and ``pos`` where the
+    batch starts in the FULL epoch order (``order[pos:pos + len(ids)] == ids``; this rank's shard offset included), so a device copy
+    of the order can be sliced with it.  Same slicing: contiguous per-rank shard (parallel.shard_range), then fixed-size batches."""
+    idx = list(range(n)) if order is None else list(order)
+    lo, hi = parallel.shard_range(len(idx), rank, world, drop_last=True)
+    idx = idx[lo:hi]
+    for s in range(0, len(idx) - (batch_size - 1 if drop_last else 0), batch_size):
+        yield lo + s, idx[s:s + batch_size]
+
+
+def build_store(dataset, config):
+    """The DeviceClipStore of a training / validation set on ``config.device``: an HDF5VideoDataset is read file by file (each
+    opened once, DeviceClipStore.from_hdf5), any other map-style dataset item by item."""
+    from .data.dataset import HDF5VideoDataset
+    from .data.device_store import DeviceClipStore
+    if isinstance(dataset, HDF5VideoDataset):
+        return DeviceClipStore.from_hdf5(dataset.hdf5_path, dataset.flow_path, dataset.transform, dataset.num_frames, dataset.max_frames,
+                                         device=config.device, motion_key=config.motion_key)
+    return DeviceClipStore.from_dataset(dataset, config.device, motion_key=config.motion_key)
 
 
 def _model_forward(model, batch, config):
@@ -217,6 +242,15 @@ class ModelTrainer:
         bucket = int(getattr(config, "graph_bucket", 1))
         self._graphed_eval = GraphedEvalForward(model, config, bucket=bucket) if getattr(config, "use_graphs", False) else None
         self._graphed_train = None
+        self._train_store = self._val_store = None
+        if getattr(config, "device_store", False):
+            # both sets in device memory, batches assembled there (vmc_gather_clips).  Every rank holds the full store: the per-epoch
+            # permutation touches every video.
+            from ..graphs import pooled_stream
+            self._train_store, self._val_store = (build_store(ds, config) for ds in (train_set, val_set))
+            self._store_pooled = pooled_stream(model)
+            self._store_out = {}                       # (B, T_rgb, T_motion) -> the captured steps' static batch buffers
+            self._val_order = torch.arange(len(self._val_store), dtype=torch.int32, device=config.device)
         if getattr(config, "use_graphs", False):
             # captured training steps: step count / lr / dropout seeds in device memory (optim.FusedAdam.enable_device_state).
             # One process: the whole step is one graph.  Data parallel: forward + backward graph, the gradient exchange, optimiser graph.
@@ -224,10 +258,15 @@ class ModelTrainer:
             ragged = dict(bucket=bucket, pooled=pooled_stream(model))
             self.optimizer.enable_device_state(base_seed=config.seed if world == 1 else config.seed * 1000 + rank)
             model.use_device_seeds(self.optimizer)
-            if world == 1:
-                self._graphed_train = GraphedTrainStep(self._device_state_step, self.optimizer, **ragged)
+            if self._train_store is not None:
+                # the graph is keyed on (T_rgb, T_motion) by value and holds its own gather: bucketing happens in padded_lengths
+                ragged, step, fwd_bwd = dict(bucket=1, pooled=None), self._store_step, self._store_fwd_bwd
             else:
-                self._graphed_train = GraphedTrainStep(self._device_state_fwd_bwd, self.optimizer, exchange=self.reducer.all_reduce,
+                step, fwd_bwd = self._device_state_step, self._device_state_fwd_bwd
+            if world == 1:
+                self._graphed_train = GraphedTrainStep(step, self.optimizer, **ragged)
+            else:
+                self._graphed_train = GraphedTrainStep(fwd_bwd, self.optimizer, exchange=self.reducer.all_reduce,
                                                        opt_fn=self._device_state_update, **ragged)
         if world == 1 and os.environ.get("VMC_ADAM_OVERLAP", "0") == "1":
             # AdamW of a finished layer on a side stream beside the backward of the layers below it.  Bit-identical, but measured
@@ -264,6 +303,65 @@ class ModelTrainer:
         output.backward(dlogits)
         return loss, output.detach()
 
+    # ---- device-resident store path (config.device_store) -------------------------------------------------------------------
+    def _store_batch(self, idx, T_rgb, T_motion):
+        """Gather into the static buffers of this shape -> (rgb, motion, mask_rgb, mask_motion, labels, pool_len).  pool_len: the
+        store's max_len tensor of the pooled stream; None in the concatenation modes, which keep exact T_out."""
+        mk = self.config.motion_key
+        b = self._train_store.gather(idx, T_rgb, T_motion, out=self._store_buffers(int(idx.shape[0]), T_rgb, T_motion))
+        pool_len = None if self._store_pooled is None else b[f"max_len_{mk}" if self._store_pooled == "motion" else "max_len_rgb"]
+        return b["embeddings"], b[f"{mk}_embeddings"], b["mask_rgb"], b[f"mask_{mk}"], b["labels"], pool_len
+
+    def _store_buffers(self, B, T_rgb, T_motion):
+        out = self._store_out.get((B, T_rgb, T_motion))
+        if out is None:
+            out = self._store_out[(B, T_rgb, T_motion)] = self._train_store.alloc_out(B, T_rgb, T_motion)
+        return out
+
+    def _store_step(self, idx, T_rgb, T_motion):
+        """The one-graph step fed from the store: gather + tick + forward + loss + backward + AdamW."""
+        rgb, mot, mr, mf, labels, pool_len = self._store_batch(idx, T_rgb, T_motion)
+        return self._device_state_step(rgb, mot, mr, mf, labels, pool_len=pool_len) + (labels,)
+
+    def _store_fwd_bwd(self, idx, T_rgb, T_motion):
+        """The data-parallel step's first graph fed from the store."""
+        rgb, mot, mr, mf, labels, pool_len = self._store_batch(idx, T_rgb, T_motion)
+        return self._device_state_fwd_bwd(rgb, mot, mr, mf, labels, pool_len=pool_len) + (labels,)
+
+    def _store_lengths(self, store, ids):
+        """(T_rgb, T_motion) of a batch: bucketed where the model pools under pool_len, exact in the concatenation modes."""
+        bucket = int(getattr(self.config, "graph_bucket", 1)) if (self._graphed_train is not None and self._store_pooled is not None) else 1
+        return store.padded_lengths(ids, bucket)
+
+    def _train_epoch_store(self, order):
+        """The body of train_epoch with every batch assembled on the device: the host sends B indices per step (already there:
+        the epoch's permutation is moved once) and picks the padded lengths from the store's host length arrays."""
+        store, cfg = self._train_store, self.config
+        total, n = torch.zeros((), device=cfg.device), 0
+        order_dev = torch.tensor(order, dtype=torch.int32, device=cfg.device)
+        for pos, ids in index_batches(len(store), cfg.batch_size, self.rank, self.world, order=order):
+            idx = order_dev[pos:pos + len(ids)]
+            T_rgb, T_motion = self._store_lengths(store, ids)
+            if self._graphed_train is not None:
+                self._store_buffers(len(ids), T_rgb, T_motion)          # allocated here, not inside a capture's warm-up stream
+                loss, output, labels = self._graphed_train(idx, T_rgb, T_motion)
+                loss, output = loss.clone(), output.clone()
+            else:
+                batch = store.gather(idx, T_rgb, T_motion)
+                output, labels = self._forward(batch)
+                loss = self.criterion(output, labels)
+                loss.backward()
+                self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
+            total += loss.detach()
+            n += 1
+            self.mAP_metric.update(output, labels.to(dtype=torch.int))
+        return total, n
+
+    def _val_batches_store(self):
+        store, cfg = self._val_store, self.config
+        for pos, ids in index_batches(len(store), cfg.batch_size, self.rank, self.world):
+            yield store.gather(self._val_order[pos:pos + len(ids)], *store.padded_lengths(ids, 1))    # exact T_out; fresh buffers
+
     def train_epoch(self, epoch):
         self.model.train()
         self.mAP_metric.reset()
@@ -272,6 +370,10 @@ class ModelTrainer:
         order = torch.randperm(len(self.train_set), generator=g).tolist()
         if self._graphed_train is not None:
             self.optimizer.sync_hyper()                     # the epoch's learning rate -> device memory
+        if self._train_store is not None:
+            total, n = self._train_epoch_store(order)
+            stats = parallel.all_reduce_scalars(torch.stack([total, torch.tensor(float(n), device=total.device)]))
+            return float(stats[0] / stats[1].clamp(min=1)), float(self.mAP_metric.compute(distributed=self.world > 1))
         for batch in batches(self.train_set, self.config.batch_size, self.rank, self.world, order=order, motion_key=self.config.motion_key):
             if self._graphed_train is not None:
                 dev, mk = self.config.device, self.config.motion_key
@@ -295,7 +397,8 @@ class ModelTrainer:
         self.mAP_metric.reset()
         total, n = torch.zeros((), device=self.config.device), 0
         with torch.no_grad():
-            it = batches(self.val_set, self.config.batch_size, self.rank, self.world, motion_key=self.config.motion_key)
+            it = (self._val_batches_store() if self._val_store is not None else
+                  batches(self.val_set, self.config.batch_size, self.rank, self.world, motion_key=self.config.motion_key))
             pairs = self._graphed_eval.pipelined(it) if self._graphed_eval is not None else ((b, self._forward(b)[0]) for b in it)
             for batch, output in pairs:
                 labels = batch["labels"].to(self.config.device)
@@ -455,11 +558,14 @@ def main(default_task="multilabel", default_motion_key="flow"):
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--d-model", type=int, default=None)
     ap.add_argument("--dropout", type=float, default=None)
+    ap.add_argument("--device-store", action="store_true", help="hold the embedding sets in device memory and assemble batches there")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
     over = {k: v for k, v in dict(epochs=args.epochs, batch_size=args.batch_size, d_model=args.d_model, dropout=args.dropout,
                                   mlp_dropout=args.dropout).items() if v is not None}
     over.update(task=args.task, device=f"cuda:{local}")
+    if args.device_store:
+        over["device_store"] = True
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

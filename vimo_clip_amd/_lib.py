@@ -110,6 +110,7 @@ SIGNATURES = {
     "vmc_grad_clip_workspace_bytes": (Z, [Z]),
     "vmc_grad_clip_dev": (I, [P, Z, P, P, P, Z, P]),
     "vmc_sumsq": (I, [P, Z, P, P]),
+    "vmc_gather_clips": (I, [P, I, P, I, ctypes.c_longlong, I, P, P, I, P, P]),
 }
 
 

@@ -126,6 +126,11 @@ class GraphedTrainStep:
         self.bucket, self.pooled = int(bucket), pooled
         self._lens = _PoolLens()
 
+    @property
+    def n_graphs(self) -> int:
+        """Step graphs captured so far (one per distinct input shape / value key)."""
+        return len(self._graphs)
+
     def _live(self):
         o, a = self.opt, self.opt.arena
         live = (a.flat_param, a.flat_grad, o.m, o.v, o.dev_state, o.dev_hyper)
