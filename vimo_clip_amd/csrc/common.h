@@ -110,7 +110,8 @@ template <int ACT>
 __device__ inline float apply_act(float x) {
   // x * sigmoid(1.702 x) with one v_exp_f32 and one v_rcp_f32 (1 ulp each; the result is rounded to 16 bits anyway)
   if (ACT == VMC_ACT_QUICKGELU) return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.4554669595930156f * x));
-  if (ACT == VMC_ACT_GELU_ERF) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f));
+  // x Phi(x) with Phi = erfc(-x / sqrt 2) / 2: 1 + erf cancels in the left tail (x = -5: 8 % off, x <= -5.6: a flat zero)
+  if (ACT == VMC_ACT_GELU_ERF) return 0.5f * x * erfcf(x * -0.70710678118654752f);
   if (ACT == VMC_ACT_RELU) return fmaxf(x, 0.0f);
   return x;
 }
@@ -129,8 +130,8 @@ __device__ inline float act_grad_rt(float x, int act) {
       return s * (1.0f + 1.702f * x * (1.0f - s));
     }
     case VMC_ACT_GELU_ERF: {
-      float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-      float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+      float cdf = 0.5f * erfcf(x * -0.70710678118654752f);      // as apply_act: no cancellation in the left tail
+      float pdf = 0.3989422804014327f * expf(-0.5f * x * x);      // expf: v_exp_f32 alone flushes the results below 2^-126 that bf16 still holds
       return cdf + x * pdf;
     }
     case VMC_ACT_RELU: return x > 0.0f ? 1.0f : 0.0f;

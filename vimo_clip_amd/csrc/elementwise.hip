@@ -871,7 +871,11 @@ __global__ void act_bwd_kernel(const uint16_t* __restrict__ x, const uint16_t* _
       }
       *(uint4*)(dx + i) = make_uint4(o[0], o[1], o[2], o[3]);
     } else {
-      for (size_t k = i; k < n; ++k) dx[k] = T::from_f32(T::to_f32(dy[k]) * act_grad_rt(T::to_f32(x[k]), act));
+      for (size_t k = i; k < n; ++k) {
+        float v = T::to_f32(dy[k]) * act_grad_rt(T::to_f32(x[k]), act);
+        asm volatile("" : "+v"(v));      // a product of its own, as in the body: folded into the f16 conversion (v_fma_mixlo_f16, addend +0) -0 became +0
+        dx[k] = T::from_f32(v);
+      }
     }
   }
 }
