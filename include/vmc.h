@@ -110,6 +110,35 @@ int vmc_frame_diff_gray_u8(const uint8_t* frames, const uint8_t* prev, uint8_t* 
                            long long stride_t, long long stride_c, long long stride_y, long long stride_x,
                            int w_r, int w_g, int w_b, int shift, int channels_out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Bilinear resize of u8 frames, bit-exact with the MammalNet student's data path: dataset_frame_diff_mn.py:82-91
+ * (frames.float() / 255 -> F.interpolate(size, mode="bilinear", align_corners=False), aten's CPU kernels) and the to_pil_image that
+ * follows in the student (pic.mul(255).byte()).  The operation order is part of the contract (DESIGN.md "Bilinear resize"):
+ * float32 throughout, one rounding per operation, scale = (float)in / (float)out, src = fma(scale, d + 0.5, -0.5) clamped at 0,
+ * p(v) = v / 255 correctly rounded, then one of aten's two recipes:
+ *   VMC_RESIZE_SEPARABLE  row = fma(lx0, p0, lx1 * p1), out = fma(ly0, row0, ly1 * row1)            (its generic kernel)
+ *   VMC_RESIZE_WEIGHTS4   w_yx = ly_y * lx_x, out = fma(w11, p11, fma(w10, p10, fma(w00, p00, w01 * p01)))   (its channels-last kernel)
+ * aten (torch 2.10, AVX-512) runs the second on contiguous frames when OH + OW <= VMC_RESIZE_ATEN_SMALL, and for three-channel
+ * frames whenever the process has ONE thread (a DataLoader worker); the first otherwise.  Neither flag = the choice aten makes in a
+ * multi-threaded process: by output size.  q = (u8) trunc(out * 255) is the same for both.
+ *   src      u8, F frames of C planes of H x W addressed by BYTE strides: element (f, c, y, x) at
+ *            src + f*s_f + c*s_c + y*s_y + x*s_x.  [T,H,W,3] stacks and [F,C,H,W] tensors are read in place.
+ *   dst      contiguous [F,C,OH,OW]: f32 `out` (what _resize_frames returns), or with VMC_RESIZE_U8 the u8 `q` (the pixels
+ *            to_pil_image makes of it).  H == OH && W == OW needs no special case: p(v) as f32, v as u8, by either recipe.
+ *   out_mode 0 (f32) or VMC_RESIZE_U8, optionally | one recipe flag.
+ * VMC_E_ARG, before any launch: src or dst NULL, F / H / W / OH / OW < 1, C not 1 or 3, out_mode negative, with unknown bits or with
+ * both recipe flags.  VMC_E_SHAPE: more than 2^31 - 1 blocks of 8 rows x 256 columns.
+ * HBM: the source once + 4 B (f32) or 1 B (u8) per output sample; 16-byte / 4-byte stores where four outputs sit at an aligned
+ * address, scalar stores of the same values elsewhere (csrc/resize_bilinear.hip). */
+enum { VMC_RESIZE_U8 = 1, VMC_RESIZE_SEPARABLE = 2, VMC_RESIZE_WEIGHTS4 = 4 };
+#define VMC_RESIZE_ATEN_SMALL 128
+int vmc_resize_bilinear_u8(const uint8_t* src, void* dst, int F, int C, int H, int W, int OH, int OW,
+                           long long s_f, long long s_c, long long s_y, long long s_x, int out_mode, void* stream);
+/* out[i] = (u8)((int)trunc(x[i] * 255) & 255), the product rounded to f32 first: to_pil_image on a float picture.  Specified for
+ * 0 <= x <= 255 (the reference's cast is undefined outside); [0,1] floats give their PIL pixels, integer-valued floats v give
+ * (256 - v) mod 256, the wrap of SURVEY.md §7 quirk 1.  x f32 [n], out u8 [n].  VMC_E_ARG: x or out NULL, n < 1. */
+int vmc_unit_f32_to_u8(const float* x, uint8_t* out, long long n, void* stream);
+
 /* Pillow-exact antialiased resample of planar u8 images [planes, in_h, in_w] along one axis — the BICUBIC
  * ``Resize`` of clip._transform (models/student_model.py:77-78) and of CLIPImageProcessor (extract_embeddings.py:91),
  * both of which call PIL.Image.resize.  out pixel o (of the resampled axis) = clip8((2^21 + sum_t in[lo_o + t] *

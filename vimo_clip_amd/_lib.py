@@ -31,6 +31,8 @@ SIGNATURES = {
     "vmc_preprocess_patches_gray_u8": (I, [P, P, I, I, I, I, I, I, P]),
     "vmc_patches_gray_u8_exact": (I, [P, P, I, I, I, I, I, I, P]),
     "vmc_frame_diff_gray_u8": (I, [P, P, P, I, I, I] + [ctypes.c_longlong] * 4 + [I, I, I, I, I, P]),
+    "vmc_resize_bilinear_u8": (I, [P, P, I, I, I, I, I, I] + [ctypes.c_longlong] * 4 + [I, P]),
+    "vmc_unit_f32_to_u8": (I, [P, P, ctypes.c_longlong, P]),
     "vmc_resample_u8": (I, [P, P, P, P, I, I, I, I, I, I, I, I, P]),
     "vmc_linear": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, F, I, I, I, I, I, P]),
     "vmc_linear_preact": (I, [P, P, P, P, P, P, I, I, I, I, I, I, I, I, I, F, I, I, I, I, I, P]),

@@ -11,7 +11,8 @@ Differences that are deliberate and documented:
   * the per-frame CPU loop ``to_pil_image -> CLIP preprocess`` (:77-78) runs as HIP kernels: Pillow-exact
     bicubic resize + centre crop (preprocess.py) when the frames are not already 224x224, then normalisation
     fused with patch extraction; the float->PIL wrap-around (v -> (256 - v) mod 256) is
-    reproduced bit-exactly for u8 / integer-valued inputs.
+    reproduced bit-exactly for u8 / integer-valued inputs, and floating-point input goes through to_pil_image's own
+    ``mul(255).byte()`` (ops.unit_f32_to_u8), which covers the MammalNet dataset's [0,1] frames as well.
 """
 from __future__ import annotations
 
@@ -85,24 +86,31 @@ class FlowStudentModel(nn.Module):
         _init_linear(self.classification_head[2])
         self.to(device)
 
-    def _frames_u8(self, flow_videos):
+    def _frames_u8(self, flow_videos, unit_u8=False):
+        """[B,T,C,H,W] -> (u8 frames [B*T,C,H,W] on the device, wrap_quirk): the pixels ``to_pil_image(frame)`` holds (:78), or the
+        pixels whose wrap v -> (256 - v) mod 256 gives them."""
         B, T, C, H, W = flow_videos.shape
         fr = flow_videos.reshape(B * T, C, H, W)      # any H x W: Resize(R, BICUBIC) + CenterCrop(R) run PIL-exact on the GPU
-        if fr.dtype != torch.uint8:
-            # the reference casts to float and to_pil_image multiplies by 255 and wraps to u8 (:74,:78);
-            # integer-valued floats in 0..255 are the same pixels as their u8 cast
-            fr = fr.to(torch.uint8)
-        return fr.to(self.device)
+        if fr.dtype == torch.uint8:
+            # u8 stands for the integer-valued floats the AK datasets hand over: the reference casts to float and to_pil_image
+            # multiplies by 255 and wraps to u8 (:74,:78).  unit_u8: already the PIL pixels (ops.resize_bilinear_u8(as_u8=True))
+            return fr.to(self.device), not unit_u8
+        if fr.is_floating_point():
+            # to_pil_image itself, pic.mul(255).byte(): [0,1] floats (dataset_frame_diff_mn.py) become their pixels, integer-valued
+            # floats 0..255 the wrapped pixels, the same bytes the u8 route makes of them
+            return ops.unit_f32_to_u8(fr.to(self.device).float()), False
+        return fr.to(torch.uint8).to(self.device), True
 
-    def forward(self, flow_videos):
-        """flow_videos [B,T,3,H,W] -> (embeddings [B,T,E], embeddings_for_distillation [B,T,E], logits [B,C])."""
+    def forward(self, flow_videos, *, unit_u8=False):
+        """flow_videos [B,T,3,H,W] -> (embeddings [B,T,E], embeddings_for_distillation [B,T,E], logits [B,C]).
+        unit_u8: u8 input is taken as pixels already quantised the way to_pil_image quantises [0,1] floats (no wrap)."""
         B, T = flow_videos.shape[:2]
-        frames = self._frames_u8(flow_videos)
+        frames, wrap = self._frames_u8(flow_videos, unit_u8)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         if train:
-            emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=True)          # [B*T, E] f32
+            emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=wrap)          # [B*T, E] f32
         else:
-            emb = self.visual_encoder.encode_frames_u8(frames, wrap_quirk=True)
+            emb = self.visual_encoder.encode_frames_u8(frames, wrap_quirk=wrap)
         return self._heads(emb, train, B, T)
 
     def _heads(self, emb, train, B, T):

@@ -336,6 +336,58 @@ def _restride_like(prev: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
     return buf
 
 
+RESIZE_RECIPES = {"aten": 0, "separable": 2, "weights4": 4}      # VMC_RESIZE_SEPARABLE / VMC_RESIZE_WEIGHTS4 (include/vmc.h)
+RESIZE_ATEN_SMALL = 128                                          # VMC_RESIZE_ATEN_SMALL
+
+
+def resize_bilinear_u8(frames_u8: torch.Tensor, size, out: torch.Tensor = None, as_u8: bool = False, recipe: str = "aten") -> torch.Tensor:
+    """Bilinear resize of u8 frames (vmc_resize_bilinear_u8), bit-exact with the reference's dataset_frame_diff_mn.py
+    ``F.interpolate(frames.float() / 255, size, mode="bilinear", align_corners=False)`` on the CPU.
+    recipe: aten's CPU kernel has two operation orders (DESIGN.md "Bilinear resize").  "aten" takes the one aten takes in a
+    multi-threaded process ("weights4" when OH + OW <= RESIZE_ATEN_SMALL, else "separable"); a one-thread process, such as a
+    DataLoader worker, runs "weights4" on three-channel frames of any size.
+    frames_u8: u8 device tensor [F,C,H,W], C 1 or 3, any strides (a permuted [T,H,W,3] stack is read in place).
+    Returns contiguous [F,C,OH,OW]: f32 in [0,1], or with as_u8 the u8 pixels ``to_pil_image`` makes of it (``.mul(255).byte()``).
+    out: optional contiguous device tensor of that shape and dtype to write into (e.g. one sample's slice of a batch)."""
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+        raise ValueError("frames must be a 4-D u8 tensor [F,C,H,W]")
+    F, C, H, W = frames_u8.shape
+    if C not in (1, 3):
+        raise ValueError(f"frames must have 1 or 3 channels, got {C}")
+    OH, OW = (int(v) for v in size)
+    if OH < 1 or OW < 1:
+        raise ValueError("size must be positive")
+    if recipe not in RESIZE_RECIPES:
+        raise ValueError(f"recipe must be one of {sorted(RESIZE_RECIPES)}")
+    shape, dtype = (F, C, OH, OW), (torch.uint8 if as_u8 else torch.float32)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=frames_u8.device)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != frames_u8.device:
+        raise ValueError(f"out must be a contiguous {dtype} tensor of shape {shape} on the frames' device")
+    src, dst = ptr(frames_u8), ptr(out)
+    if F == 0:
+        return out
+    if H < 1 or W < 1:
+        raise ValueError("frames must not be empty")
+    s_f, s_c, s_y, s_x = frames_u8.stride()
+    check(lib.vmc_resize_bilinear_u8(src, dst, F, C, H, W, OH, OW, s_f, s_c, s_y, s_x, int(as_u8) | RESIZE_RECIPES[recipe], stream()),
+          "resize_bilinear_u8")
+    return out
+
+
+def unit_f32_to_u8(x: torch.Tensor) -> torch.Tensor:
+    """u8 tensor of x's shape with (int)trunc(x * 255) & 255 (vmc_unit_f32_to_u8): the pixels ``to_pil_image`` makes of a float picture.
+    [0,1] floats give their PIL pixels; integer-valued floats v in 0..255 give (256 - v) mod 256."""
+    if x.dtype != torch.float32:
+        raise ValueError("x must be float32")
+    x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    src = ptr(x)
+    if x.numel():
+        check(lib.vmc_unit_f32_to_u8(src, ptr(out), x.numel(), stream()), "unit_f32_to_u8")
+    return out
+
+
 def patches_f32_split(pixel_values: torch.Tensor, patch: int, dtype16) -> torch.Tensor:
     """[F*g*g, 3*kpad] = [x_hi | x_lo | x_hi] (vmc_patches_f32_split)."""
     F, C, R, R2 = pixel_values.shape

@@ -27,10 +27,10 @@ def embed_dim(clip_model_name: str) -> int:
     return vit_geometry(clip_model_name)[5]
 
 
-def _batches(ds, batch_size, rank, world):
+def _batches(ds, batch_size, rank, world, collate=collate_fn):
     lo, hi = parallel.shard_range(len(ds), rank, world)
     for s in range(lo, hi - batch_size + 1, batch_size):
-        yield collate_fn([ds[i] for i in range(s, s + batch_size)])
+        yield collate([ds[i] for i in range(s, s + batch_size)])
 
 
 def _frames(batch):
@@ -43,12 +43,13 @@ def _class_loss(logits, labels, class_positive_weight, single_label):
     return classification_loss(logits, labels, positive_weight=class_positive_weight)
 
 
-def evaluate(model, val_set, device, distillation_loss_mode, class_positive_weight, batch_size, rank=0, world=1, single_label=False):
+def evaluate(model, val_set, device, distillation_loss_mode, class_positive_weight, batch_size, rank=0, world=1, single_label=False,
+             collate=collate_fn, forward_kwargs=None):
     model.eval()
     tot = torch.zeros(4, device=device)
     with torch.no_grad():
-        for batch in _batches(val_set, batch_size, rank, world):
-            _, emb_d, logits = model(_frames(batch).to(device))
+        for batch in _batches(val_set, batch_size, rank, world, collate):
+            _, emb_d, logits = model(_frames(batch).to(device), **(forward_kwargs or {}))
             dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=distillation_loss_mode)
             cl = _class_loss(logits, batch["labels"].to(device), class_positive_weight, single_label)
             tot += torch.stack([dl, cl, dl + cl, torch.ones((), device=device)])
@@ -57,12 +58,18 @@ def evaluate(model, val_set, device, distillation_loss_mode, class_positive_weig
     return float(tot[0]) / n, float(tot[1]) / n, float(tot[2]) / n
 
 
-def train(args):
+def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
+    """datasets: a (train_set, val_set) pair built by the caller instead of the ones the arguments name; collate: its collate function,
+    called with the list of samples (a device-side one is bound to its device by the caller); forward_kwargs: keyword arguments of
+    every model call (train_frame_diff_mn.py passes ``unit_u8=True`` with its device-side collate)."""
     rank, world, local = parallel.init_from_env()
     device = f"cuda:{local}"
     E = embed_dim(args.clip_model_name)
     single = bool(getattr(args, "single_label", False))
-    if getattr(args, "clip_embeddings_dir", None):
+    forward_kwargs = forward_kwargs or {}
+    if datasets is not None:
+        train_set, val_set = datasets
+    elif getattr(args, "clip_embeddings_dir", None):
         from .dataset import HDF5VideoDataset
         train_set = HDF5VideoDataset(args.clip_embeddings_dir, args.flow_videos_dir, sequence_length=args.sequence_length)
         val_set = HDF5VideoDataset(args.val_clip_embeddings_dir or args.clip_embeddings_dir, args.val_flow_videos_dir or args.flow_videos_dir,
@@ -80,16 +87,17 @@ def train(args):
     for epoch in range(args.epochs):
         model.train()
         t0, nframes = time.time(), 0
-        for batch in _batches(train_set, args.batch_size, rank, world):
+        for batch in _batches(train_set, args.batch_size, rank, world, collate):
             frames = _frames(batch)
-            emb, emb_d, logits = model(frames.to(device))
+            emb, emb_d, logits = model(frames.to(device), **forward_kwargs)
             dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
             cl = _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
             (dl + cl).backward()
             optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=None if single else args.grad_clip_norm)
             nframes += frames.shape[0] * frames.shape[1]
         torch.cuda.synchronize()
-        vd, vc, vt = evaluate(model, val_set, device, args.distillation_loss_mode, args.class_positive_weight, args.batch_size, rank, world, single)
+        vd, vc, vt = evaluate(model, val_set, device, args.distillation_loss_mode, args.class_positive_weight, args.batch_size, rank, world, single,
+                              collate, forward_kwargs)
         if rank == 0 and ckpt_dir:                          # train.py:164-172: every epoch + the best-so-far copy
             from .checkpoint import save_state_dict
             save_state_dict(model, f"{ckpt_dir}/student_epoch_{epoch + 1}.pth")

@@ -1,0 +1,54 @@
+"""MammalNet student training — the reference's train_frame_diff_mn.py on the MI355X engine: train.train with the MammalNet
+dataset (dataset_frame_diff_mn.py: ``trimmed_videos/<id>`` HDF5 layout, bilinear-resized frame-difference frames in [0,1]) and the
+single-label loss (CrossEntropy on ``labels.argmax(1)``, no gradient clipping; :82,102,108).  Same argument names as the reference
+(its spelling with hyphens is accepted too).  ``--device_resize`` keeps the decoded frames u8, uploads 1 B per source sample and
+resizes + quantises them on the GPU (bit-exact with the host path, DESIGN.md "Bilinear resize").
+"""
+from __future__ import annotations
+
+import argparse
+import functools
+import os
+
+from .dataset_frame_diff_mn import HDF5VideoDataset, collate_fn, collate_fn_device
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Train diff_frame-only student model, MammalNet variant (MI355X engine)")
+
+    def arg(name, **kw):
+        p.add_argument("--" + name, "--" + name.replace("_", "-"), dest=name, **kw)
+
+    arg("epochs", type=int, default=10)
+    arg("batch_size", type=int, default=32)
+    arg("num_workers", type=int, default=4, help="accepted for the reference's command lines; batches are assembled in-process")
+    arg("learning_rate", type=float, default=1e-3)
+    arg("distillation_loss_mode", default="cosine", choices=["cosine", "mse"])
+    arg("num_classes", type=int, default=12)
+    arg("sequence_length", type=int, default=30)
+    arg("residual_alpha", type=float, default=0.1)
+    arg("train_hdf5_path", required=True, help="HDF5 file of teacher embeddings, training split (trimmed_videos/<id>/embeddings, labels)")
+    arg("val_hdf5_path", required=True)
+    arg("frame_diff_videos_dir", required=True)
+    arg("spatial_size", type=int, nargs=2, default=(224, 224), metavar=("H", "W"))
+    arg("clip_model_name", default="ViT-B/32")
+    arg("checkpoint_dir", default=None)
+    arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
+    return p
+
+
+def train(args):
+    from . import train as student_train
+    size = tuple(args.spatial_size)
+    sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
+                                  raw_u8=args.device_resize) for path in (args.train_hdf5_path, args.val_hdf5_path))
+    args.single_label, args.class_positive_weight, args.grad_clip_norm = True, 1, None
+    if not args.device_resize:
+        return student_train.train(args, datasets=sets, collate=collate_fn)
+    device = f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}"          # the device train.train gives this rank
+    collate = functools.partial(collate_fn_device, spatial_size=size, device=device)
+    return student_train.train(args, datasets=sets, collate=collate, forward_kwargs={"unit_u8": True})
+
+
+if __name__ == "__main__":
+    train(build_parser().parse_args())
