@@ -673,6 +673,33 @@ int vmc_gather_clips(const vmc_clip_stream* streams, int n_streams /* 1 or 2 */,
                      long long n_videos, int D, const float* labels /* [n_videos, C] or NULL */, float* labels_out /* [B, C] */,
                      int C, int* status /* device, one int32, may be NULL */, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * K18 — device-resident epoch log: what the TFAM loops keep per step for the epoch's loss and metric (TFAM/train_and_eval.py
+ * :86-87,119-122: the logits rows, the label rows, the running loss), appended at a cursor in device memory.  A captured training
+ * step then logs itself and the host reads the log once per epoch instead of once per step.
+ *   One call, all on the device (enqueue only, no allocation, no synchronisation, safe under capture), with rows = state[0]:
+ *   - rows < 0 or rows + B > capacity: status bit 1 is set and NOTHING else is written -- no row, no counter, no loss.
+ *   - otherwise the B rows of `values` are copied to values[rows .. rows + B) bit for bit; `targets` receives every label truncated
+ *     toward zero (labels.to(torch.int)) and clamped into 0..255 (NaN: 0); status bit 2 is set if a truncated label is not 0 or 1;
+ *     squash[rows .. rows + B) = f, f = 1 iff ANY of the B * C values of this call is < 0 or > 1 -- torchmetrics' rule for applying
+ *     a sigmoid to an update call, as IEEE comparisons: NaN, -0.0, 0.0 and 1.0 do not set it;
+ *   - then loss_sum += *loss (one fp32 add; skipped when loss is NULL), steps += 1, rows += B.
+ *   state: [0] rows, [1] steps (accepted calls), [2] status (sticky), [3] reserved.  The host zeroes state and loss_sum to start an
+ *   epoch and reads them when it likes.
+ *   One launch of one workgroup with 4-byte accesses (the destination offset rows * C is a device value of unknown alignment);
+ *   the counters are written by one thread with plain stores, no atomics: the same bits on every call and every replay.
+ * VMC_E_ARG, before any launch: log / values / targets or a pointer field of the log NULL, B / C / capacity <= 0. */
+typedef struct vmc_metric_log {
+  float* values;      /* [capacity, C] fp32: the rows exactly as they were handed in (logits or probabilities) */
+  uint8_t* targets;   /* [capacity, C] labels truncated toward zero, as labels.to(torch.int) */
+  uint8_t* squash;    /* [capacity] 1: the append call this row came with had a value < 0 or > 1 */
+  int* state;         /* [4] int32: rows, steps, status, reserved */
+  float* loss_sum;    /* [1] fp32 */
+  int capacity, C;
+} vmc_metric_log;
+int vmc_metric_append(const vmc_metric_log* log, const float* values /* [B, C] */, const float* targets /* [B, C] */,
+                      const float* loss /* device, 1 element, or NULL */, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@ class Config:
         self.graph_bucket = 1      # use_graphs with ragged loaders: pad clip lengths to multiples of this, one graph per bucket (graphs.pad_to_bucket)
         self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
         self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
+        self.device_metrics = False  # log logits / labels / loss on the device inside the step, read once per epoch (metrics.DeviceMetricLog)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
 
@@ -70,6 +71,8 @@ class Config:
             kw["grad_clip_norm"] = float(t["grad_clip_norm"])
         if "device_store" in t:                     # optional as well
             kw["device_store"] = bool(t["device_store"])
+        if "device_metrics" in t:                   # optional as well
+            kw["device_metrics"] = bool(t["device_metrics"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -251,16 +254,24 @@ class ModelTrainer:
             self._store_pooled = pooled_stream(model)
             self._store_out = {}                       # (B, T_rgb, T_motion) -> the captured steps' static batch buffers
             self._val_order = torch.arange(len(self._val_store), dtype=torch.int32, device=config.device)
+        self._train_log = self._val_log = None
+        if getattr(config, "device_metrics", False):
+            # the epoch's bookkeeping in device memory (vmc_metric_append): the step appends its logits, labels and loss, the loops
+            # below read once per epoch.  Capacity: the rows this rank sees per epoch (shard, then whole batches, as index_batches).
+            from ..metrics import DeviceMetricLog
+            self._train_log, self._val_log = (DeviceMetricLog(max(1, self._epoch_rows(len(ds))), config.num_classes, config.task, config.device)
+                                              for ds in (train_set, val_set))
+        extra = dict(extra_live=self._train_log.state_tensors()) if self._train_log is not None else {}
         if getattr(config, "use_graphs", False):
             # captured training steps: step count / lr / dropout seeds in device memory (optim.FusedAdam.enable_device_state).
             # One process: the whole step is one graph.  Data parallel: forward + backward graph, the gradient exchange, optimiser graph.
             from ..graphs import GraphedTrainStep, pooled_stream
-            ragged = dict(bucket=bucket, pooled=pooled_stream(model))
+            ragged = dict(bucket=bucket, pooled=pooled_stream(model), **extra)
             self.optimizer.enable_device_state(base_seed=config.seed if world == 1 else config.seed * 1000 + rank)
             model.use_device_seeds(self.optimizer)
             if self._train_store is not None:
                 # the graph is keyed on (T_rgb, T_motion) by value and holds its own gather: bucketing happens in padded_lengths
-                ragged, step, fwd_bwd = dict(bucket=1, pooled=None), self._store_step, self._store_fwd_bwd
+                ragged, step, fwd_bwd = dict(bucket=1, pooled=None, **extra), self._store_step, self._store_fwd_bwd
             else:
                 step, fwd_bwd = self._device_state_step, self._device_state_fwd_bwd
             if world == 1:
@@ -275,6 +286,17 @@ class ModelTrainer:
             self.optimizer.enable_backward_overlap(model.parameter_groups_by_layer())
             model.grad_group_callback = self.optimizer.group_ready
 
+    def _epoch_rows(self, n_items):
+        """Rows this rank logs in one epoch over ``n_items`` videos: its shard (parallel.shard_range), whole batches only."""
+        lo, hi = parallel.shard_range(n_items, self.rank, self.world, drop_last=True)
+        return (hi - lo) // self.config.batch_size * self.config.batch_size
+
+    def _epoch_stats(self, log):
+        """(mean loss, metric) of an epoch from its device log: the one read, then what the loops do with [total, n]."""
+        rows, steps, _, loss_sum = log.read()
+        stats = parallel.all_reduce_scalars(torch.tensor([loss_sum, float(steps)], dtype=torch.float32, device=self.config.device))
+        return float(stats[0] / stats[1].clamp(min=1)), float(log.compute(distributed=self.world > 1, rows=rows))
+
     def _forward(self, batch):
         return _model_forward(self.model, batch, self.config), batch["labels"].to(self.config.device)
 
@@ -287,6 +309,8 @@ class ModelTrainer:
         loss, dlogits = loss_and_grad(self.criterion, output, labels)      # criterion(output, labels); loss.backward() (:81-83)
         output.backward(dlogits)
         self._device_state_update()
+        if self._train_log is not None:
+            self._train_log.append(output.detach(), labels, loss)
         return loss, output.detach()
 
     def _device_state_update(self):
@@ -301,6 +325,8 @@ class ModelTrainer:
         output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)
         output.backward(dlogits)
+        if self._train_log is not None:
+            self._train_log.append(output.detach(), labels, loss)
         return loss, output.detach()
 
     # ---- device-resident store path (config.device_store) -------------------------------------------------------------------
@@ -336,7 +362,7 @@ class ModelTrainer:
     def _train_epoch_store(self, order):
         """The body of train_epoch with every batch assembled on the device: the host sends B indices per step (already there:
         the epoch's permutation is moved once) and picks the padded lengths from the store's host length arrays."""
-        store, cfg = self._train_store, self.config
+        store, cfg, log = self._train_store, self.config, self._train_log
         total, n = torch.zeros((), device=cfg.device), 0
         order_dev = torch.tensor(order, dtype=torch.int32, device=cfg.device)
         for pos, ids in index_batches(len(store), cfg.batch_size, self.rank, self.world, order=order):
@@ -345,6 +371,8 @@ class ModelTrainer:
             if self._graphed_train is not None:
                 self._store_buffers(len(ids), T_rgb, T_motion)          # allocated here, not inside a capture's warm-up stream
                 loss, output, labels = self._graphed_train(idx, T_rgb, T_motion)
+                if log is not None:
+                    continue                                            # the step logged itself
                 loss, output = loss.clone(), output.clone()
             else:
                 batch = store.gather(idx, T_rgb, T_motion)
@@ -352,6 +380,9 @@ class ModelTrainer:
                 loss = self.criterion(output, labels)
                 loss.backward()
                 self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
+                if log is not None:
+                    log.append(output, labels, loss)
+                    continue
             total += loss.detach()
             n += 1
             self.mAP_metric.update(output, labels.to(dtype=torch.int))
@@ -370,8 +401,13 @@ class ModelTrainer:
         order = torch.randperm(len(self.train_set), generator=g).tolist()
         if self._graphed_train is not None:
             self.optimizer.sync_hyper()                     # the epoch's learning rate -> device memory
+        log = self._train_log
+        if log is not None:
+            log.reset()
         if self._train_store is not None:
             total, n = self._train_epoch_store(order)
+            if log is not None:
+                return self._epoch_stats(log)
             stats = parallel.all_reduce_scalars(torch.stack([total, torch.tensor(float(n), device=total.device)]))
             return float(stats[0] / stats[1].clamp(min=1)), float(self.mAP_metric.compute(distributed=self.world > 1))
         for batch in batches(self.train_set, self.config.batch_size, self.rank, self.world, order=order, motion_key=self.config.motion_key):
@@ -380,15 +416,22 @@ class ModelTrainer:
                 labels = batch["labels"].to(dev)
                 loss, output = self._graphed_train(batch["embeddings"].to(dev), batch[f"{mk}_embeddings"].to(dev),
                                                    batch["mask_rgb"].to(dev), batch[f"mask_{mk}"].to(dev), labels)
+                if log is not None:
+                    continue                                            # the step logged itself
                 loss, output = loss.clone(), output.clone()
             else:
                 output, labels = self._forward(batch)
                 loss = self.criterion(output, labels)
                 loss.backward()
                 self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
+                if log is not None:
+                    log.append(output, labels, loss)
+                    continue
             total += loss.detach()
             n += 1
             self.mAP_metric.update(output, labels.to(dtype=torch.int))
+        if log is not None:
+            return self._epoch_stats(log)
         stats = parallel.all_reduce_scalars(torch.stack([total, torch.tensor(float(n), device=total.device)]))
         return float(stats[0] / stats[1].clamp(min=1)), float(self.mAP_metric.compute(distributed=self.world > 1))
 
@@ -396,15 +439,23 @@ class ModelTrainer:
         self.model.eval()
         self.mAP_metric.reset()
         total, n = torch.zeros((), device=self.config.device), 0
+        log = self._val_log
+        if log is not None:
+            log.reset()
         with torch.no_grad():
             it = (self._val_batches_store() if self._val_store is not None else
                   batches(self.val_set, self.config.batch_size, self.rank, self.world, motion_key=self.config.motion_key))
             pairs = self._graphed_eval.pipelined(it) if self._graphed_eval is not None else ((b, self._forward(b)[0]) for b in it)
             for batch, output in pairs:
                 labels = batch["labels"].to(self.config.device)
+                if log is not None:                                     # on the consumer's stream, in batch order
+                    log.append(output, labels, self.criterion(output, labels))
+                    continue
                 total += self.criterion(output, labels)
                 n += 1
                 self.mAP_metric.update(output, labels.to(dtype=torch.int))
+        if log is not None:
+            return self._epoch_stats(log)
         stats = parallel.all_reduce_scalars(torch.stack([total, torch.tensor(float(n), device=total.device)]))
         return float(stats[0] / stats[1].clamp(min=1)), float(self.mAP_metric.compute(distributed=self.world > 1))
 
@@ -559,6 +610,7 @@ def main(default_task="multilabel", default_motion_key="flow"):
     ap.add_argument("--d-model", type=int, default=None)
     ap.add_argument("--dropout", type=float, default=None)
     ap.add_argument("--device-store", action="store_true", help="hold the embedding sets in device memory and assemble batches there")
+    ap.add_argument("--device-metrics", action="store_true", help="log loss and metric inputs on the device inside the step, read once per epoch")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
     over = {k: v for k, v in dict(epochs=args.epochs, batch_size=args.batch_size, d_model=args.d_model, dropout=args.dropout,
@@ -566,6 +618,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
     over.update(task=args.task, device=f"cuda:{local}")
     if args.device_store:
         over["device_store"] = True
+    if args.device_metrics:
+        over["device_metrics"] = True
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

@@ -113,6 +113,7 @@ SIGNATURES = {
     "vmc_grad_clip_dev": (I, [P, Z, P, P, P, Z, P]),
     "vmc_sumsq": (I, [P, Z, P, P]),
     "vmc_gather_clips": (I, [P, I, P, I, ctypes.c_longlong, I, P, P, I, P, P]),
+    "vmc_metric_append": (I, [P, P, P, P, I, P]),
 }
 
 

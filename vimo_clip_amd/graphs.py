@@ -7,6 +7,8 @@ forward is ~90 kernels of a few microseconds each: replay removes the per-launch
 """
 from __future__ import annotations
 
+import gc
+
 import torch
 
 
@@ -72,8 +74,16 @@ class GraphedCallable:
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self.static_outputs = fn(*self.static_inputs)
+        # No cyclic garbage collection inside the capture: a collected cycle may own captured graphs of its own (a dropped trainer and
+        # its GraphedTrainStep reference each other), and releasing their memory pools while a stream captures aborts the process.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.graph):
+                self.static_outputs = fn(*self.static_inputs)
+        finally:
+            if gc_was_on:
+                gc.enable()
 
     def __call__(self, *inputs):
         for dst, src in zip(self.static_inputs, inputs):
@@ -110,10 +120,13 @@ class GraphedTrainStep:
     ``step_fn`` hands to ``AMO_CLIP.forward(pool_len=...)``.  The graph key uses the padded lengths, so one graph serves a whole
     bucket, exactly (see pad_to_bucket).  ``pooled``: the stream the model pools (``pooled_stream(model)``); None keeps exact
     shapes, as ``bucket = 1`` does.  Dropout masks are a function of the padded shape (element index ``row * N + col``): a
-    bucketed step draws other masks than an unbucketed one, and the same masks as an eager step on the same padded tensors."""
+    bucketed step draws other masks than an unbucketed one, and the same masks as an eager step on the same padded tensors.
+
+    ``extra_live``: further tensors that ``step_fn`` modifies in place and that a warm-up run must leave as it found them (the
+    cursor and sums of a metrics.DeviceMetricLog appended to inside the step); saved and restored with the optimiser's."""
 
     def __init__(self, step_fn, optimizer, max_graphs: int = 16, exchange=None, opt_fn=None, graph_factory=None, bucket: int = 1,
-                 pooled="rgb"):
+                 pooled="rgb", extra_live=()):
         if getattr(optimizer, "dev_state", None) is None:
             raise ValueError("GraphedTrainStep needs FusedAdam.enable_device_state()")
         if (exchange is None) != (opt_fn is None):
@@ -125,17 +138,28 @@ class GraphedTrainStep:
         self._opt_graph = None
         self.bucket, self.pooled = int(bucket), pooled
         self._lens = _PoolLens()
+        self.extra_live = tuple(extra_live)
 
     @property
     def n_graphs(self) -> int:
         """Step graphs captured so far (one per distinct input shape / value key)."""
         return len(self._graphs)
 
+    @staticmethod
+    def _key(inputs):
+        return tuple((tuple(x.shape), x.dtype) if torch.is_tensor(x) else x for x in inputs)
+
+    def captured(self, *inputs):
+        """The captured step graph that ``__call__(*inputs)`` would replay (exact shapes: ``bucket = 1`` callers), None when that
+        shape has not been captured.  For tools that replay a step without the host work around it."""
+        return self._graphs.get(self._key(inputs))
+
     def _live(self):
         o, a = self.opt, self.opt.arena
         live = (a.flat_param, a.flat_grad, o.m, o.v, o.dev_state, o.dev_hyper)
         clip = getattr(o, "dev_clip", None)            # device-side gradient clipping in use: its norm / coefficient slots too
-        return live if clip is None else live + (clip,)
+        live = live if clip is None else live + (clip,)
+        return live + self.extra_live
 
     def _capture(self, fn, inputs):
         from . import autograd_ops
@@ -164,7 +188,7 @@ class GraphedTrainStep:
         if self.bucket > 1 and self.pooled is not None:
             rgb, mot, mr, mf, n = pad_to_bucket(*inputs[:4], self.bucket, self.pooled)
             inputs = (rgb, mot, mr, mf) + tuple(inputs[4:]) + (self._lens.get(n, rgb.device),)
-        key = tuple((tuple(x.shape), x.dtype) if torch.is_tensor(x) else x for x in inputs)
+        key = self._key(inputs)
         g = self._graphs.get(key)
         if g is None:
             if len(self._graphs) >= self.max_graphs:           # too many shapes: eager step (same device-state arithmetic)
