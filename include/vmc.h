@@ -417,14 +417,18 @@ int vmc_distill_loss(const float* student, const float* teacher, float* loss, fl
                      int rows, int E, int rows_per_clip, size_t teacher_clip_stride, int mode_cosine,
                      void* workspace, size_t workspace_bytes, void* stream);
 /* BCE-with-logits, pos_weight = pw*y + 1 (losses.py:59-67; pw < 0 means "None" -> weight 1; also
- * nn.BCEWithLogitsLoss of TFAM/train_and_eval.py:58).  logits/targets f32 [n]; mean over n. */
+ * nn.BCEWithLogitsLoss of TFAM/train_and_eval.py:58).  logits/targets f32 [n]; mean over n.
+ * dlogits = [(1 - y) sigmoid(x) - w y sigmoid(-x)] / n with w = pw*y + 1, each sigmoid formed without a subtraction: every
+ * element keeps its relative accuracy in both confident tails. */
 int vmc_bce_loss(const float* logits, const float* targets, float* loss, float* dlogits, int n, float pos_weight,
                  void* workspace, size_t workspace_bytes, void* stream);
 /* Softmax cross entropy, mean over rows — nn.CrossEntropyLoss() of the MammalNet (single-label) variants:
  * train_frame_diff_mn.py:82,102 passes class indices (``labels.argmax(dim=1)``), TFAM/train_and_eval_frame_diff_MN.py:59,83
  * passes the float one-hot rows themselves (probability targets).  Exactly one of target_index (int64 [rows]) and
  * target_prob (f32 [rows,C]) is non-NULL.  logits f32 [rows,C]; loss f32[1]; dlogits f32 [rows,C] or NULL;
- * workspace >= vmc_loss_workspace_bytes(rows). */
+ * workspace >= vmc_loss_workspace_bytes(rows).
+ * A row's loss is sum(y) log(sum exp(x - m)) - sum_c y_c (x_c - m), m = max x: accurate relative to log C and the loss itself,
+ * whatever the size of the logits.  dlogits = (softmax(x) sum(y) - y) / rows. */
 int vmc_cross_entropy_loss(const float* logits, const long long* target_index, const float* target_prob, float* loss,
                            float* dlogits, int rows, int C, void* workspace, size_t workspace_bytes, void* stream);
 

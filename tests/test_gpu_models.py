@@ -666,10 +666,11 @@ def test_grouped_weight_gradients_equal_the_per_linear_launches():
 def test_fused_adam_and_copy_refresh_equals_the_two_kernel_step(dtype):
     """vmc_adam_cast_multi (AdamW + refresh of both 16-bit copies from the registers, one pass over the masters) against
     vmc_adam_step_dev + vmc_cast_weights_multi: masters, moments and every compute copy bit for bit over 4 steps -- matrices with
-    both / one / no cached copy, ragged and non-multiple-of-4 shapes, 1-D parameters."""
+    both / one / no cached copy, ragged and non-multiple-of-4 shapes, 1-D parameters down to a single element.  vmc_adam_step_dev itself is
+    pinned to float64 in test_gpu_loss_optim_kernels.py, which closes the chain."""
     from vimo_clip_amd import autograd_ops as ag
     from vimo_clip_amd.optim import FusedAdam, GradArena
-    shapes = [(192, 128), (100, 72), (130, 50), (33,), (64, 64), (7, 9), (256,), (96, 3, 4, 4)]
+    shapes = [(192, 128), (100, 72), (130, 50), (33,), (64, 64), (7, 9), (256,), (96, 3, 4, 4), (13,), (1,)]
 
     def build(fused):
         ps = [torch.nn.Parameter(synth.normal(8, f"p{i}", sh).cuda()) for i, sh in enumerate(shapes)]
