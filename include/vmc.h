@@ -3,7 +3,7 @@
  *
  * The reference (MarcosRodrigoT/VIMO-CLIP) has no FFI: its hot path sits behind Python nn.Module /
  * function signatures and runs on stock PyTorch ATen ops.  Each entry point below replaces the ATen
- * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17 is this project's own).
+ * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17..K19 are this project's own).
  * The Python mirror of the reference interface (vimo_clip_amd/) calls these through ctypes.
  *
  * Conventions
@@ -703,6 +703,31 @@ typedef struct vmc_metric_log {
 } vmc_metric_log;
 int vmc_metric_append(const vmc_metric_log* log, const float* values /* [B, C] */, const float* targets /* [B, C] */,
                       const float* loss /* device, 1 element, or NULL */, int B, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K19 — token concatenation at device-resident lengths: the token-concatenation mode's torch.cat([rgb[:, :-1], motion], 1)
+ * (TFAM/models/AMO_CLIP.py:153-156) for streams that were zero-padded beyond their own lengths, with the real rows as a PREFIX of
+ * the output, so that one "POOL LENGTH" value (above) serves the concatenated sequence and a captured forward or step replays for
+ * every batch of a length bucket.  After the per-stream positional encoding nothing in the layers depends on a row's position: rows
+ * 0..n-1 below are exactly the reference's concatenation at the batch's own lengths, the rows behind them are masked as keys, stay
+ * out of the pool and receive a zero gradient.
+ *   len_rgb / len_motion: ONE int32 each in DEVICE memory, read at kernel start (the "POOL LENGTH" convention): the streams' own
+ *   lengths n_rgb / n_motion.  NULL = T_rgb / T_motion.  The host cannot validate device memory, so the kernel clamps:
+ *     nr = clamp(*len_rgb, 1, T_rgb);  nm = clamp(*len_motion, 1, T_motion);
+ *     keep = min(nr - 1, T_out);  nm = min(nm, T_out - keep);  n = keep + nm  (1 <= n <= T_out).
+ *   x    [B, T_out, D] fp32: rgb[b, t] for t < keep, motion[b, t - keep] for keep <= t < n, 0 for n <= t < T_out (exact copies).
+ *   mask [B, T_out] u8: the source masks' bytes in the same layout, 1 where a source mask pointer is NULL, 0 on rows n..T_out-1.
+ *   pool_len[0] = n, one plain store.
+ *   EVERY element of x, mask and pool_len is written on every call (the outputs may be uninitialised; a graph replay never sees the
+ *   previous batch), and for any device values nothing outside the buffers is read or written.  With NULL lengths and
+ *   T_out = T_rgb - 1 + T_motion the outputs are the reference's torch.cat of tokens and masks.
+ *   16-byte accesses where D % 4 == 0 and rgb, motion and x are 16-byte aligned, 4-byte accesses otherwise (neither is an error).
+ *   The call only enqueues: no allocation, no synchronisation, safe under capture.
+ * VMC_E_ARG, before any launch: rgb / motion / x / mask / pool_len NULL.  VMC_E_SHAPE: B / T_rgb / T_motion / T_out / D <= 0,
+ * B > 65535. */
+int vmc_concat_tokens_len(const float* rgb, const float* motion, const uint8_t* mask_rgb /* [B, T_rgb] or NULL */,
+                          const uint8_t* mask_motion /* [B, T_motion] or NULL */, float* x, uint8_t* mask, int* pool_len, int B,
+                          int T_rgb, int T_motion, int T_out, int D, const int* len_rgb, const int* len_motion, void* stream);
 
 #ifdef __cplusplus
 }

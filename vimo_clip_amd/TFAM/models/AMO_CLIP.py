@@ -250,9 +250,10 @@ class AMO_CLIP(nn.Module):
                 out.append(p)
         return out
 
-    def _fused_inputs(self, rgb_emb, motion_emb, m_rgb, m_flow, training):
+    def _fused_inputs(self, rgb_emb, motion_emb, m_rgb, m_flow, training, concat=None):
         """(x, mask, motion, mask_kv, cross) of the fused chains for the configured fusion mode, or None when the mode / shapes are
-        outside their set (the per-op path then runs)."""
+        outside their set (the per-op path then runs).  ``concat``: the (tokens, mask) that ``forward(token_lens=...)`` built for a
+        concatenation mode, in place of the exact-shape concatenation."""
         from ... import tfam_fused as tf
         from ... import tfam_train as tt
         dt16 = self.compute_dtype
@@ -267,12 +268,15 @@ class AMO_CLIP(nn.Module):
             rgb_cut = rgb_emb[:, :-1, :]
             m_cut = m_rgb[:, :-1] if m_rgb is not None else None
             if self.concat_dim == 1:
-                x = torch.cat([rgb_cut, motion_emb], dim=1)                   # token concat: memory plumbing
-                m = torch.cat([m_cut, m_flow], dim=1).contiguous() if m_cut is not None else None
+                if concat is not None:
+                    x, m = concat
+                else:
+                    x = torch.cat([rgb_cut, motion_emb], dim=1)               # token concat: memory plumbing
+                    m = torch.cat([m_cut, m_flow], dim=1).contiguous() if m_cut is not None else None
             else:
                 if training:                          # the projection layer's gradient needs d(tokens): per-op path
                     return None
-                xcat = torch.cat([rgb_cut, motion_emb], dim=-1)
+                xcat = concat[0] if concat is not None else torch.cat([rgb_cut, motion_emb], dim=-1)
                 if not tf.supported(self, xcat.shape[0], xcat.shape[1], 0, False):
                     return None
                 x = ag.linear(ag.cast(_f32c(xcat).view(-1, xcat.shape[-1]), dt16), self.projection_layer.weight,
@@ -283,22 +287,22 @@ class AMO_CLIP(nn.Module):
             return None
         return _f32c(x), m, (_f32c(motion) if cross else None), m_kv, cross
 
-    def _forward_fused(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None):
+    def _forward_fused(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None, concat=None):
         """Eval forward through vmc_tfam_forward (one call: hoisted K|V GEMM + 6 launches per layer + pool + head).
         Returns None when the shapes are outside the fused chain's set; the per-op path below then runs."""
         from ... import tfam_fused as tf
-        sel = self._fused_inputs(rgb_emb, motion_emb, m_rgb, m_flow, False)
+        sel = self._fused_inputs(rgb_emb, motion_emb, m_rgb, m_flow, False, concat)
         if sel is None:
             return None
         x, m, motion, m_kv, cross = sel
         pack = tf.get_pack(self, self.compute_dtype).refresh()
         return pack.forward(x, motion, m, m_kv, cross, slot=getattr(self, "fused_slot", 0), pool_len=pool_len)
 
-    def _forward_fused_train(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None):
+    def _forward_fused_train(self, rgb_emb, motion_emb, m_rgb, m_flow, pool_len=None, concat=None):
         """Train-mode forward + (through autograd) backward as the fused launch chains of tfam_train.py: one autograd node for the
         whole model.  None when the mode / shapes are outside the chain's set."""
         from ... import tfam_train as tt
-        sel = self._fused_inputs(rgb_emb, motion_emb, m_rgb, m_flow, True)
+        sel = self._fused_inputs(rgb_emb, motion_emb, m_rgb, m_flow, True, concat)
         if sel is None:
             return None
         x, m, motion, m_kv, cross = sel
@@ -308,10 +312,11 @@ class AMO_CLIP(nn.Module):
     def pools_padded_tokens(self) -> bool:
         """True for the fusion modes whose pooled stream may be zero-padded further under ``pool_len`` (cross attention, rgb-only,
         flow-only).  The two concatenation modes drop "the last padded position" with ``rgb_emb[:, :-1]`` (:153-154): more padding
-        would change which row is dropped, so they take exact shapes only."""
+        would change which row is dropped, so under ``pool_len`` they take exact shapes only; ``forward(token_lens=...)`` is their
+        own way of running padded (the concatenation is rebuilt with the real rows first)."""
         return bool(self.use_only_rgb or self.use_only_flow or self.use_cross_attention)
 
-    def forward(self, rgb_emb, motion_emb, mask_rgb=None, mask_flow=None, *, pool_len=None):
+    def forward(self, rgb_emb, motion_emb, mask_rgb=None, mask_flow=None, *, pool_len=None, token_lens=None, concat_len=None):
         """The reference's four arguments, plus ``pool_len`` (None | int | one-element int32 device tensor): the logical length of
         the stream that is pooled (RGB tokens in cross and rgb-only mode, motion tokens in flow-only mode).  The classifier then
         sees the mean over rows 0..pool_len-1 of every clip instead of all T rows, and rows pool_len..T-1 receive a zero
@@ -319,9 +324,39 @@ class AMO_CLIP(nn.Module):
         gives the logits and gradients of the unpadded batch.  The kernels read the value from device memory, so a captured
         forward or step pools over the value of each replay; an int becomes a device tensor here (not allowed while capturing).
         Dropout masks are indexed by the PADDED shape (element ``row * N + col`` of the padded tensors): a padded step draws
-        other masks than the unpadded one, and the same masks as an eager step on the same padded tensors."""
+        other masks than the unpadded one, and the same masks as an eager step on the same padded tensors.
+
+        ``token_lens = (n_rgb, n_motion)`` (each an int or a one-element int32 device tensor, the rules of ``pool_len``) is the same
+        service for the two concatenation modes, whose streams were each zero-padded beyond their own lengths
+        (graphs.pad_concat_to_bucket).  Nothing behind the per-stream positional encoding depends on a row's position, so the
+        concatenation is rebuilt with the real rows as a prefix and one pool length does the rest:
+          concat_dim = 1:  x = [rgb rows 0..n_rgb-2 | motion rows 0..n_motion-1 | zeros up to ``concat_len``], the key mask laid out
+                           the same way, pooled over n_rgb - 1 + n_motion rows (vmc_concat_tokens_len, include/vmc.h K19: the
+                           split position is a device value).  ``concat_len``: the host int T_out, default T_rgb - 1 + T_motion.
+          concat_dim = -1: x = projection(cat([rgb[:, :T_motion], motion], -1)) on the padded tensors (needs T_rgb >= T_motion) with
+                           the motion mask, pooled over n_motion rows: the RGB row the reference drops lands at row n_motion,
+                           which is masked and not pooled.  ``mask_flow`` is required.
+        Rows 0..n-1 are the reference's concatenation at the batch's own lengths; the rows behind them are masked as keys, stay
+        out of the pool and receive a zero gradient.  The token tensors must not require grad (the kernel has no backward)."""
         dt16, D = self.compute_dtype, self.d_model
         dev = self.device
+        if token_lens is not None:
+            if self.pools_padded_tokens:
+                raise ValueError("token_lens is for the two concatenation fusion modes only (use_cross_attention=False without "
+                                 "use_only_rgb / use_only_flow); the other modes take pool_len")
+            if pool_len is not None:
+                raise ValueError("token_lens and pool_len exclude each other: the pool length follows from token_lens")
+            if rgb_emb.requires_grad or motion_emb.requires_grad:
+                raise ValueError("token_lens: the token tensors must not require grad (the concatenation kernel has no backward)")
+            if self.concat_dim != 1 and mask_flow is None:
+                raise ValueError("token_lens with concat_dim = -1 needs mask_flow: the padded rows would be attended to")
+            if self.concat_dim != 1 and rgb_emb.shape[1] < motion_emb.shape[1]:
+                raise ValueError("token_lens with concat_dim = -1 needs T_rgb >= T_motion")
+            if len(token_lens) != 2 or token_lens[0] is None or token_lens[1] is None:
+                raise ValueError("token_lens must be (n_rgb, n_motion)")
+            token_lens = tuple(ops.pool_len_tensor(n, rgb_emb.device if rgb_emb.is_cuda else dev) for n in token_lens)
+        elif concat_len is not None:
+            raise ValueError("concat_len comes with token_lens")
         if pool_len is not None:
             if not self.pools_padded_tokens:
                 raise ValueError("pool_len is not supported with the concatenation fusion modes (use_cross_attention=False without "
@@ -336,12 +371,21 @@ class AMO_CLIP(nn.Module):
         m_rgb, m_flow = _mask_u8(mask_rgb, dev), _mask_u8(mask_flow, dev)
         seed_fn = self._next_seed
         self._seed_site = -1                              # device-seed mode: call sites are numbered from 0 in every forward
+        concat = None
+        if token_lens is not None:                        # after the positional encoding: the rows keep their own stream's phase
+            if self.concat_dim == 1:
+                T_out = int(concat_len) if concat_len is not None else rgb_emb.shape[1] - 1 + motion_emb.shape[1]
+                xc, mc, pool_len = ops.concat_tokens(_f32c(rgb_emb), _f32c(motion_emb), m_rgb, m_flow, T_out, *token_lens)
+                concat = (xc, mc)
+            else:
+                concat = (torch.cat([rgb_emb[:, :motion_emb.shape[1], :], motion_emb], dim=-1), m_flow)
+                pool_len = token_lens[1]
         if self.fused_inference and not self.training and not torch.is_grad_enabled():
-            out = self._forward_fused(rgb_emb, motion_emb, m_rgb, m_flow, pool_len)
+            out = self._forward_fused(rgb_emb, motion_emb, m_rgb, m_flow, pool_len, concat)
             if out is not None:
                 return out
         if self.fused_training and self.training and torch.is_grad_enabled():
-            out = self._forward_fused_train(rgb_emb, motion_emb, m_rgb, m_flow, pool_len)
+            out = self._forward_fused_train(rgb_emb, motion_emb, m_rgb, m_flow, pool_len, concat)
             if out is not None:
                 return out
             self._seed_site = -1                          # nothing was drawn on a path that declined
@@ -370,11 +414,14 @@ class AMO_CLIP(nn.Module):
             rgb_cut = rgb_emb[:, :-1, :]
             m_cut = m_rgb[:, :-1] if m_rgb is not None else None
             if self.concat_dim == 1:
-                xcat = torch.cat([rgb_cut, motion_emb], dim=1)                 # token concat: memory plumbing
-                m = torch.cat([m_cut, m_flow], dim=1).contiguous() if m_cut is not None else None
+                if concat is not None:
+                    xcat, m = concat
+                else:
+                    xcat = torch.cat([rgb_cut, motion_emb], dim=1)             # token concat: memory plumbing
+                    m = torch.cat([m_cut, m_flow], dim=1).contiguous() if m_cut is not None else None
                 x, T = flat(xcat), xcat.shape[1]
             else:
-                xcat = torch.cat([rgb_cut, motion_emb], dim=-1)
+                xcat = concat[0] if concat is not None else torch.cat([rgb_cut, motion_emb], dim=-1)
                 T = xcat.shape[1]
                 x = ag.linear(ag.cast(flat(xcat), dt16), self.projection_layer.weight, self.projection_layer.bias, out_f32=True)
                 m = m_flow

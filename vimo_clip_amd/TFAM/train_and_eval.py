@@ -37,6 +37,7 @@ class Config:
         self.dropout, self.mlp_dropout, self.device, self.checkpoint_dir, self.log_dir = 0.1, 0.1, "cuda", "checkpoints", "logs"
         self.task, self.motion_key, self.use_graphs = "multilabel", "flow", False    # use_graphs: hipGraph replay of the eval forward
         self.graph_bucket = 1      # use_graphs with ragged loaders: pad clip lengths to multiples of this, one graph per bucket (graphs.pad_to_bucket)
+        self.graph_bucket_concat = False  # graph_bucket > 1 also for the two concatenation modes (graphs.pad_concat_to_bucket, AMO_CLIP.forward(token_lens=))
         self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
         self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
         self.device_metrics = False  # log logits / labels / loss on the device inside the step, read once per epoch (metrics.DeviceMetricLog)
@@ -67,6 +68,8 @@ class Config:
             kw["motion_key"] = "frame_diff"
         if "graph_bucket" in t:                     # not a key of the reference's YAML: optional
             kw["graph_bucket"] = int(t["graph_bucket"])
+        if "graph_bucket_concat" in t:              # optional as well
+            kw["graph_bucket_concat"] = bool(t["graph_bucket_concat"])
         if t.get("grad_clip_norm") is not None:     # optional as well
             kw["grad_clip_norm"] = float(t["grad_clip_norm"])
         if "device_store" in t:                     # optional as well
@@ -139,14 +142,17 @@ class GraphedEvalForward:
     batch's own padded length (AMO_CLIP.py:169), so the padded batch carries that length as ``pool_len`` -- a device value the
     captured pool kernel reads at replay time -- and its logits are those of the unpadded batch (graphs.pad_to_bucket; up to
     the kernel choice the other length implies, i.e. within the usual tolerance rather than bit for bit).  The concatenation
-    modes cannot be padded (AMO_CLIP.pools_padded_tokens) and keep exact shapes whatever ``bucket`` says.  Only for
+    modes cannot be padded under ``pool_len`` (AMO_CLIP.pools_padded_tokens) and keep exact shapes whatever ``bucket`` says,
+    unless ``concat_bucket`` is set: their batches then go through ``graphs.pad_concat_to_bucket`` and carry both streams' own
+    lengths as ``token_lens`` (two device values) and the padded concatenated length T_out in the graph key.  Only for
     ``model.eval()`` under ``no_grad`` (no dropout, no optimiser state inside the graph)."""
 
-    def __init__(self, model, config, bucket=1, max_graphs=32, streams=2):
-        from ..graphs import _PoolLens, pooled_stream
+    def __init__(self, model, config, bucket=1, max_graphs=32, streams=2, concat_bucket=False):
+        from ..graphs import _PoolLens, concat_mode, pooled_stream
         self.model, self.config, self.max_graphs = model, config, max_graphs
         self.pooled = pooled_stream(model)
-        self.bucket = int(bucket) if self.pooled is not None else 1
+        self.concat = concat_mode(model) if concat_bucket else None
+        self.bucket = int(bucket) if (self.pooled is not None or self.concat is not None) else 1
         self._lens = _PoolLens()
         self._graphs = {}
         # Two batches in flight: an evaluation loop's batches are independent, and at the reference batch size a forward is a
@@ -158,14 +164,26 @@ class GraphedEvalForward:
         self._rr = -1
 
     def _run(self, batch, slot):
-        from ..graphs import GraphedCallable, pad_to_bucket
+        from ..graphs import GraphedCallable, pad_concat_to_bucket, pad_to_bucket
         dev, mk = self.config.device, self.config.motion_key
         rgb, mot = batch["embeddings"].to(dev), batch[f"{mk}_embeddings"].to(dev)
         mr, mf = batch["mask_rgb"].to(dev), batch[f"mask_{mk}"].to(dev)
-        rgb, mot, mr, mf, n = pad_to_bucket(rgb, mot, mr, mf, self.bucket, self.pooled)
+        T_out = None
+        if self.concat is not None:
+            rgb, mot, mr, mf, nr, nm, T_out = pad_concat_to_bucket(rgb, mot, mr, mf, self.bucket, self.concat)
+            n = None
+        else:
+            rgb, mot, mr, mf, n = pad_to_bucket(rgb, mot, mr, mf, self.bucket, self.pooled)
         key = (slot, rgb.shape[0], rgb.shape[1], mot.shape[1], rgb.shape[2])
         self.model.fused_slot = slot
-        if n is None:                                   # exact shapes
+        if T_out is not None:                           # a concatenation mode, both streams padded: T_out by value in the key
+            key = key + (T_out,)
+            args = (rgb, mot, mr, mf, self._lens.get(nr, rgb.device), self._lens.get(nm, rgb.device))
+
+            def fwd(a, b, c, d, e, f):
+                with torch.no_grad():
+                    return self.model(a, b, mask_rgb=c, mask_flow=d, token_lens=(e, f), concat_len=T_out)
+        elif n is None:                                 # exact shapes
             args = (rgb, mot, mr, mf)
 
             def fwd(a, b, c, d):
@@ -243,7 +261,10 @@ class ModelTrainer:
         self.reducer = parallel.GradientAllReducer(self.arena.flat_grad).attach(self.arena)   # buckets go out during the backward
         self.grad_clip_norm = getattr(config, "grad_clip_norm", None)
         bucket = int(getattr(config, "graph_bucket", 1))
-        self._graphed_eval = GraphedEvalForward(model, config, bucket=bucket) if getattr(config, "use_graphs", False) else None
+        bucket_concat = bool(getattr(config, "graph_bucket_concat", False))
+        self._graphed_eval = (GraphedEvalForward(model, config, bucket=bucket, concat_bucket=bucket_concat)
+                              if getattr(config, "use_graphs", False) else None)
+        self._store_concat = None                      # "time" | "feature": the store path buckets a concatenation model
         self._graphed_train = None
         self._train_store = self._val_store = None
         if getattr(config, "device_store", False):
@@ -265,13 +286,17 @@ class ModelTrainer:
         if getattr(config, "use_graphs", False):
             # captured training steps: step count / lr / dropout seeds in device memory (optim.FusedAdam.enable_device_state).
             # One process: the whole step is one graph.  Data parallel: forward + backward graph, the gradient exchange, optimiser graph.
-            from ..graphs import GraphedTrainStep, pooled_stream
-            ragged = dict(bucket=bucket, pooled=pooled_stream(model), **extra)
+            from ..graphs import GraphedTrainStep, concat_mode, pooled_stream
+            concat = concat_mode(model) if (bucket_concat and bucket > 1) else None
+            ragged = dict(bucket=bucket, pooled=pooled_stream(model), concat=concat, **extra)
             self.optimizer.enable_device_state(base_seed=config.seed if world == 1 else config.seed * 1000 + rank)
             model.use_device_seeds(self.optimizer)
             if self._train_store is not None:
                 # the graph is keyed on (T_rgb, T_motion) by value and holds its own gather: bucketing happens in padded_lengths
                 ragged, step, fwd_bwd = dict(bucket=1, pooled=None, **extra), self._store_step, self._store_fwd_bwd
+                self._store_concat = concat
+            elif concat is not None:
+                step, fwd_bwd = self._concat_step, self._concat_fwd_bwd
             else:
                 step, fwd_bwd = self._device_state_step, self._device_state_fwd_bwd
             if world == 1:
@@ -300,12 +325,12 @@ class ModelTrainer:
     def _forward(self, batch):
         return _model_forward(self.model, batch, self.config), batch["labels"].to(self.config.device)
 
-    def _device_state_step(self, rgb, mot, mr, mf, labels, pool_len=None):
+    def _device_state_step(self, rgb, mot, mr, mf, labels, pool_len=None, token_lens=None, concat_len=None):
         """tick + forward + loss + backward + AdamW with every step-dependent scalar read from device memory (pool_len: the
-        bucketed batch's own length, GraphedTrainStep)."""
+        bucketed batch's own length, GraphedTrainStep; token_lens / concat_len: the same for a concatenation model)."""
         from ..losses import loss_and_grad
         self.optimizer.tick()
-        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
+        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len, token_lens=token_lens, concat_len=concat_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)      # criterion(output, labels); loss.backward() (:81-83)
         output.backward(dlogits)
         self._device_state_update()
@@ -318,25 +343,36 @@ class ModelTrainer:
         then holds the rank sum, and grad_scale = 1 / world is already in device memory: GraphedTrainStep)."""
         self.optimizer.step(max_grad_norm=self.grad_clip_norm)
 
-    def _device_state_fwd_bwd(self, rgb, mot, mr, mf, labels, pool_len=None):
+    def _device_state_fwd_bwd(self, rgb, mot, mr, mf, labels, pool_len=None, token_lens=None, concat_len=None):
         """The data-parallel step's first graph: tick + forward + loss + backward (the exchange and AdamW follow outside it)."""
         from ..losses import loss_and_grad
         self.optimizer.tick()
-        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len)
+        output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len, token_lens=token_lens, concat_len=concat_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)
         output.backward(dlogits)
         if self._train_log is not None:
             self._train_log.append(output.detach(), labels, loss)
         return loss, output.detach()
 
+    def _concat_step(self, rgb, mot, mr, mf, labels, n_rgb, n_mot, T_out):
+        """The one-graph step of a bucketed concatenation model, in GraphedTrainStep(concat=)'s argument order."""
+        return self._device_state_step(rgb, mot, mr, mf, labels, token_lens=(n_rgb, n_mot), concat_len=T_out)
+
+    def _concat_fwd_bwd(self, rgb, mot, mr, mf, labels, n_rgb, n_mot, T_out):
+        return self._device_state_fwd_bwd(rgb, mot, mr, mf, labels, token_lens=(n_rgb, n_mot), concat_len=T_out)
+
     # ---- device-resident store path (config.device_store) -------------------------------------------------------------------
-    def _store_batch(self, idx, T_rgb, T_motion):
-        """Gather into the static buffers of this shape -> (rgb, motion, mask_rgb, mask_motion, labels, pool_len).  pool_len: the
-        store's max_len tensor of the pooled stream; None in the concatenation modes, which keep exact T_out."""
+    def _store_batch(self, idx, T_rgb, T_motion, T_out=None):
+        """Gather into the static buffers of this shape -> (rgb, motion, mask_rgb, mask_motion, labels, keywords of the step).
+        pool_len: the store's max_len tensor of the pooled stream; None in the concatenation modes, which keep exact T_out unless
+        they are bucketed (T_out given): then token_lens = both max_len tensors, straight from the gather, and concat_len = T_out."""
         mk = self.config.motion_key
         b = self._train_store.gather(idx, T_rgb, T_motion, out=self._store_buffers(int(idx.shape[0]), T_rgb, T_motion))
-        pool_len = None if self._store_pooled is None else b[f"max_len_{mk}" if self._store_pooled == "motion" else "max_len_rgb"]
-        return b["embeddings"], b[f"{mk}_embeddings"], b["mask_rgb"], b[f"mask_{mk}"], b["labels"], pool_len
+        if T_out is not None:
+            kw = dict(token_lens=(b["max_len_rgb"], b[f"max_len_{mk}"]), concat_len=T_out)
+        else:
+            kw = dict(pool_len=None if self._store_pooled is None else b[f"max_len_{mk}" if self._store_pooled == "motion" else "max_len_rgb"])
+        return b["embeddings"], b[f"{mk}_embeddings"], b["mask_rgb"], b[f"mask_{mk}"], b["labels"], kw
 
     def _store_buffers(self, B, T_rgb, T_motion):
         out = self._store_out.get((B, T_rgb, T_motion))
@@ -344,20 +380,32 @@ class ModelTrainer:
             out = self._store_out[(B, T_rgb, T_motion)] = self._train_store.alloc_out(B, T_rgb, T_motion)
         return out
 
-    def _store_step(self, idx, T_rgb, T_motion):
-        """The one-graph step fed from the store: gather + tick + forward + loss + backward + AdamW."""
-        rgb, mot, mr, mf, labels, pool_len = self._store_batch(idx, T_rgb, T_motion)
-        return self._device_state_step(rgb, mot, mr, mf, labels, pool_len=pool_len) + (labels,)
+    def _store_step(self, idx, T_rgb, T_motion, T_out=None):
+        """The one-graph step fed from the store: gather [+ token concatenation] + tick + forward + loss + backward + AdamW."""
+        rgb, mot, mr, mf, labels, kw = self._store_batch(idx, T_rgb, T_motion, T_out)
+        return self._device_state_step(rgb, mot, mr, mf, labels, **kw) + (labels,)
 
-    def _store_fwd_bwd(self, idx, T_rgb, T_motion):
+    def _store_fwd_bwd(self, idx, T_rgb, T_motion, T_out=None):
         """The data-parallel step's first graph fed from the store."""
-        rgb, mot, mr, mf, labels, pool_len = self._store_batch(idx, T_rgb, T_motion)
-        return self._device_state_fwd_bwd(rgb, mot, mr, mf, labels, pool_len=pool_len) + (labels,)
+        rgb, mot, mr, mf, labels, kw = self._store_batch(idx, T_rgb, T_motion, T_out)
+        return self._device_state_fwd_bwd(rgb, mot, mr, mf, labels, **kw) + (labels,)
 
     def _store_lengths(self, store, ids):
-        """(T_rgb, T_motion) of a batch: bucketed where the model pools under pool_len, exact in the concatenation modes."""
-        bucket = int(getattr(self.config, "graph_bucket", 1)) if (self._graphed_train is not None and self._store_pooled is not None) else 1
-        return store.padded_lengths(ids, bucket)
+        """(T_rgb, T_motion) of a batch: bucketed where the model pools under pool_len or a concatenation model is bucketed
+        (graph_bucket_concat), exact otherwise."""
+        on = self._graphed_train is not None and (self._store_pooled is not None or self._store_concat is not None)
+        return store.padded_lengths(ids, int(getattr(self.config, "graph_bucket", 1)) if on else 1)
+
+    def _store_concat_len(self, store, ids, T_motion):
+        """T_out of a bucketed concatenation batch, from the store's host length arrays: what graphs.pad_concat_to_bucket gives the
+        collated batch (None when the store path does not bucket a concatenation model)."""
+        if self._store_concat is None:
+            return None
+        if self._store_concat == "feature":
+            return T_motion
+        bucket = int(self.config.graph_bucket)
+        n_rgb, n_mot = store.padded_lengths(ids, 1)
+        return -(-(n_rgb - 1 + n_mot) // bucket) * bucket
 
     def _train_epoch_store(self, order):
         """The body of train_epoch with every batch assembled on the device: the host sends B indices per step (already there:
@@ -370,7 +418,8 @@ class ModelTrainer:
             T_rgb, T_motion = self._store_lengths(store, ids)
             if self._graphed_train is not None:
                 self._store_buffers(len(ids), T_rgb, T_motion)          # allocated here, not inside a capture's warm-up stream
-                loss, output, labels = self._graphed_train(idx, T_rgb, T_motion)
+                T_out = self._store_concat_len(store, ids, T_motion)
+                loss, output, labels = self._graphed_train(idx, T_rgb, T_motion, *(() if T_out is None else (T_out,)))
                 if log is not None:
                     continue                                            # the step logged itself
                 loss, output = loss.clone(), output.clone()
@@ -496,7 +545,8 @@ class ModelTester:
     def __init__(self, model, test_set, config, rank=0, world=1):
         self.model, self.test_set, self.config, self.rank, self.world = model, test_set, config, rank, world
         _, self.mAP_metric = task_objects(config)
-        self._graphed_eval = (GraphedEvalForward(model, config, bucket=int(getattr(config, "graph_bucket", 1)))
+        self._graphed_eval = (GraphedEvalForward(model, config, bucket=int(getattr(config, "graph_bucket", 1)),
+                                                 concat_bucket=bool(getattr(config, "graph_bucket_concat", False)))
                               if getattr(config, "use_graphs", False) else None)
 
     def load_best_model(self, checkpoint_dir):
@@ -610,6 +660,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
     ap.add_argument("--d-model", type=int, default=None)
     ap.add_argument("--dropout", type=float, default=None)
     ap.add_argument("--device-store", action="store_true", help="hold the embedding sets in device memory and assemble batches there")
+    ap.add_argument("--graph-bucket-concat", action="store_true",
+                    help="with use_graphs and graph_bucket > 1: bucket the two concatenation modes as well")
     ap.add_argument("--device-metrics", action="store_true", help="log loss and metric inputs on the device inside the step, read once per epoch")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
@@ -620,6 +672,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
         over["device_store"] = True
     if args.device_metrics:
         over["device_metrics"] = True
+    if args.graph_bucket_concat:
+        over["graph_bucket_concat"] = True
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

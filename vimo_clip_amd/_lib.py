@@ -114,6 +114,7 @@ SIGNATURES = {
     "vmc_sumsq": (I, [P, Z, P, P]),
     "vmc_gather_clips": (I, [P, I, P, I, ctypes.c_longlong, I, P, P, I, P, P]),
     "vmc_metric_append": (I, [P, P, P, P, I, P]),
+    "vmc_concat_tokens_len": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P]),
 }
 
 

@@ -45,6 +45,32 @@ def pad_to_bucket(rgb, mot, mask_rgb, mask_flow, bucket: int, pooled="rgb"):
     return pad(rgb, Tr), pad(mot, Tf), pad(mask_rgb, Tr, rgb), pad(mask_flow, Tf, mot), n
 
 
+def concat_mode(model):
+    """Which concatenation an AMO_CLIP performs: "time" (``concat_dim = 1``: tokens), "feature" (``concat_dim = -1``: features, then
+    ``projection_layer``), or None for the modes that pool one stream (``pooled_stream``)."""
+    if getattr(model, "use_only_rgb", False) or getattr(model, "use_only_flow", False) or getattr(model, "use_cross_attention", True):
+        return None
+    return "time" if model.concat_dim == 1 else "feature"
+
+
+def pad_concat_to_bucket(rgb, mot, mask_rgb, mask_flow, bucket: int, mode):
+    """``pad_to_bucket`` for the two concatenation modes: (rgb, mot, mask_rgb, mask_flow, n_rgb, n_mot, T_out).
+
+    Each stream is zero-padded to its own next multiple of ``bucket``, the masks get zeros on the new rows (a mask that is None
+    becomes all-true over the ORIGINAL length first).  n_rgb / n_mot are the original lengths, to be handed to
+    ``AMO_CLIP.forward(..., token_lens=(n_rgb, n_mot), concat_len=T_out)``, which rebuilds the concatenation with the real rows first
+    so that the padded batch gives the logits and gradients of the unpadded one.  T_out is the padded length of the concatenated
+    sequence: for "time" roundup(n_rgb - 1 + n_mot, bucket) -- the concatenated length is bucketed, not the sum of two rounded
+    lengths, which keeps clips of up to 64 concatenated tokens on the fused chains; for "feature" the padded motion length.
+    ``bucket <= 1`` or ``mode is None``: everything is returned as it came, n_rgb = n_mot = T_out = None."""
+    if bucket <= 1 or mode is None:
+        return rgb, mot, mask_rgb, mask_flow, None, None, None
+    n_rgb, n_mot = int(rgb.shape[1]), int(mot.shape[1])
+    rgb, mot, mask_rgb, mask_flow, _ = pad_to_bucket(rgb, mot, mask_rgb, mask_flow, bucket)
+    T_out = -(-(n_rgb - 1 + n_mot) // bucket) * bucket if mode == "time" else int(mot.shape[1])
+    return rgb, mot, mask_rgb, mask_flow, n_rgb, n_mot, T_out
+
+
 class _PoolLens:
     """One-element int32 tensors of the pool lengths seen so far, per device: a replay copies one into the graph's static input, and
     no step pays a host-to-device transfer for a length it has seen before."""
@@ -122,11 +148,16 @@ class GraphedTrainStep:
     shapes, as ``bucket = 1`` does.  Dropout masks are a function of the padded shape (element index ``row * N + col``): a
     bucketed step draws other masks than an unbucketed one, and the same masks as an eager step on the same padded tensors.
 
+    Concatenation models (``concat`` = ``concat_mode(model)``, "time" | "feature", with ``bucket > 1``): the first four inputs go
+    through ``pad_concat_to_bucket`` instead; ``step_fn`` receives the padded tensors, the remaining inputs, then the two length
+    tensors n_rgb and n_mot (static inputs refreshed before every replay, for ``AMO_CLIP.forward(token_lens=...)``) and, last,
+    the int T_out (``concat_len``), which is part of the graph key by value.
+
     ``extra_live``: further tensors that ``step_fn`` modifies in place and that a warm-up run must leave as it found them (the
     cursor and sums of a metrics.DeviceMetricLog appended to inside the step); saved and restored with the optimiser's."""
 
     def __init__(self, step_fn, optimizer, max_graphs: int = 16, exchange=None, opt_fn=None, graph_factory=None, bucket: int = 1,
-                 pooled="rgb", extra_live=()):
+                 pooled="rgb", extra_live=(), concat=None):
         if getattr(optimizer, "dev_state", None) is None:
             raise ValueError("GraphedTrainStep needs FusedAdam.enable_device_state()")
         if (exchange is None) != (opt_fn is None):
@@ -136,7 +167,7 @@ class GraphedTrainStep:
         self._factory = graph_factory or GraphedCallable
         self._graphs = {}
         self._opt_graph = None
-        self.bucket, self.pooled = int(bucket), pooled
+        self.bucket, self.pooled, self.concat = int(bucket), pooled, concat
         self._lens = _PoolLens()
         self.extra_live = tuple(extra_live)
 
@@ -185,7 +216,10 @@ class GraphedTrainStep:
 
     def __call__(self, *inputs):
         from . import autograd_ops
-        if self.bucket > 1 and self.pooled is not None:
+        if self.bucket > 1 and self.concat is not None:
+            rgb, mot, mr, mf, nr, nm, T_out = pad_concat_to_bucket(*inputs[:4], self.bucket, self.concat)
+            inputs = (rgb, mot, mr, mf) + tuple(inputs[4:]) + (self._lens.get(nr, rgb.device), self._lens.get(nm, rgb.device), T_out)
+        elif self.bucket > 1 and self.pooled is not None:
             rgb, mot, mr, mf, n = pad_to_bucket(*inputs[:4], self.bucket, self.pooled)
             inputs = (rgb, mot, mr, mf) + tuple(inputs[4:]) + (self._lens.get(n, rgb.device),)
         key = self._key(inputs)

@@ -427,6 +427,41 @@ def mean_pool(x: torch.Tensor, B: int, T: int, D: int, dtype16, out16=True, out3
     return o16, o32
 
 
+def concat_tokens(rgb: torch.Tensor, motion: torch.Tensor, mask_rgb, mask_motion, T_out: int, len_rgb=None, len_motion=None, out=None):
+    """(x [B, T_out, D] f32, mask [B, T_out] u8, pool_len [1] i32) = vmc_concat_tokens_len (include/vmc.h K19): the token
+    concatenation ``cat([rgb[:, :-1], motion], 1)`` at the streams' own lengths, real rows first, zeros behind them.
+    ``len_rgb`` / ``len_motion``: one-element int32 device tensors (``pool_len_tensor``) or None (the tensors' full lengths);
+    ``mask_rgb`` / ``mask_motion``: [B, T] one-byte masks (bool or uint8) or None (all real).  ``out``: (x, mask, pool_len) buffers
+    to write into; fresh ``torch.empty`` ones otherwise -- the kernel writes every element.  Only enqueues."""
+    B, T_rgb, D = rgb.shape
+    T_motion, T_out = int(motion.shape[1]), int(T_out)
+    if motion.shape[0] != B or motion.shape[2] != D:
+        raise ValueError("concat_tokens: rgb [B, T_rgb, D] and motion [B, T_motion, D] must agree in B and D")
+    for t in (rgb, motion):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("concat_tokens: need contiguous float32 token tensors")
+    masks = []
+    for m, T in ((mask_rgb, T_rgb), (mask_motion, T_motion)):
+        if m is not None:
+            if tuple(m.shape) != (B, T) or m.element_size() != 1 or not m.is_contiguous():
+                raise ValueError("concat_tokens: masks must be contiguous one-byte tensors of shape [B, T]")
+        masks.append(m)
+    for n in (len_rgb, len_motion):
+        if n is not None and (not torch.is_tensor(n) or n.dtype != torch.int32 or n.numel() != 1 or not n.is_cuda):
+            raise TypeError("concat_tokens: lengths must be one-element int32 device tensors (ops.pool_len_tensor)")
+    if out is None:
+        out = (torch.empty((B, T_out, D), dtype=torch.float32, device=rgb.device),
+               torch.empty((B, T_out), dtype=torch.uint8, device=rgb.device),
+               torch.empty(1, dtype=torch.int32, device=rgb.device))
+    x, mask, pool_len = out
+    if tuple(x.shape) != (B, T_out, D) or x.dtype != torch.float32 or not x.is_contiguous() or tuple(mask.shape) != (B, T_out) \
+            or mask.element_size() != 1 or not mask.is_contiguous() or pool_len.dtype != torch.int32 or pool_len.numel() != 1:
+        raise ValueError(f"concat_tokens: output buffers do not match B = {B}, T_out = {T_out}, D = {D}")
+    check(lib.vmc_concat_tokens_len(ptr(rgb), ptr(motion), ptr(masks[0]), ptr(masks[1]), ptr(x), ptr(mask), ptr(pool_len), B, T_rgb,
+                                    T_motion, T_out, D, ptr(len_rgb), ptr(len_motion), stream()), "concat_tokens_len")
+    return x, mask, pool_len
+
+
 def add_sinusoidal_pe_(x: torch.Tensor):
     B, T, D = x.shape
     if x.dtype != torch.float32 or not x.is_contiguous():
