@@ -591,6 +591,49 @@ int vmc_tfam_train_bwd_len(const float* dlogits, const uint8_t* mask, const uint
                            const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * K11-K14 fused, TRAINING, feature-concatenation mode — AMO_CLIP with use_cross_attention = false, concat_dim = -1
+ * (TFAM/models/AMO_CLIP.py:153-157: x = projection_layer(cat([rgb[:, :-1], motion], -1)), Linear(2 D, D)) on the same chains.
+ * The input is the materialised concatenation xcat fp32 [B*T, 2 D]; T is the motion stream's length; there is no cross
+ * attention and no motion operand.  What the chains above gain:
+ *   forward   one launch in front of layer 0: x = 16bit(xcat) Wp^T + bp (operands rounded to the compute dtype, fp32
+ *             accumulation, fp32 output: the per-op path's arithmetic).  Layer 0 reads x where it reads the caller's tokens
+ *             otherwise; the 16-bit xcat rows are saved.  28 launches at L = 4.
+ *   backward  layer 0 runs the qkv dgrad (dx0 = dy1 + dqkv Wqkv) like every other layer, into the workspace extension, with a
+ *             16-bit copy; gw_proj = dx0^T xcat and gb_proj are one more problem of the grouped weight-gradient launch that holds
+ *             layer 0's problems.  36 launches at L = 4.  No gradient wrt xcat: the tokens are data.
+ * Rows t >= *pool_len of every clip get dx0 = 0 (masked as keys by the caller, not pooled) and add nothing to either gradient.
+ * Shapes: vmc_tfam_supported(train) without cross attention, and 4 L + 1 <= 32 weight-gradient problems (L <= 7).
+ * The workspace is the training workspace with an extension behind it (vmc_tfam_train_proj_workspace_bytes >
+ * vmc_tfam_train_workspace_bytes; every offset of the latter, vmc_tfam_train_pool_grad_offset included, is unchanged), so the
+ * per-layer entries above (vmc_tfam_head_bwd_len, vmc_tfam_layer_bwd for layers L-1..1) run on it as they are; layer 0 then takes
+ * vmc_tfam_layer0_bwd_proj.  Seeds: as above (the projection has no dropout and draws none).
+ */
+typedef struct vmc_tfam_proj_params {
+  const void *w_proj;                            /* 16-bit projection_layer.weight [D, 2D] */
+  const float *b_proj;
+  float *gw_proj, *gb_proj;                      /* fp32 [D, 2D], [D]; NULL = not wanted */
+} vmc_tfam_proj_params;
+/* 0 when the shape takes these chains, else an error code */
+int vmc_tfam_proj_supported(int B, int T, int D, int H, int ff, int L, int C);
+size_t vmc_tfam_train_proj_workspace_bytes(int B, int T, int D, int H, int ff, int L, int C);
+/* Byte offset, inside that workspace, of dx0 fp32 [B*T, D], the gradient wrt the projection's output.  -1: unsupported shape. */
+long long vmc_tfam_train_proj_dx0_offset(int B, int T, int D, int H, int ff, int L, int C);
+int vmc_tfam_train_fwd_proj(const float* xcat, const vmc_tfam_proj_params* proj, const uint8_t* mask,
+                            const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, float* logits, void* workspace,
+                            size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop, float p_mlp,
+                            const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
+/* The whole backward: head, the dgrad chains of layers L-1..0, one grouped weight-gradient launch per four layers. */
+int vmc_tfam_train_bwd_proj(const float* dlogits, const vmc_tfam_proj_params* proj, const uint8_t* mask,
+                            const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
+                            size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop, float p_mlp,
+                            const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
+/* Layer 0 of the per-layer backward: its dgrad chain with the qkv dgrad, and its own grouped launch with the projection's problem.
+ * seeds: the 7 seeds of layer 0. */
+int vmc_tfam_layer0_bwd_proj(const vmc_tfam_proj_params* proj, const uint8_t* mask, const vmc_tfam_layer_params* layers,
+                             void* workspace, size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop,
+                             const uint64_t* seeds, int dtype16, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * K15 — fused Adam / AdamW over one flat fp32 buffer (train.py:66; TFAM/train_and_eval.py:53).
  *   decoupled_wd = 1: p *= 1 - lr*wd first (AdamW); 0: g += wd*p (Adam L2).
  *   grad_scale multiplies g first (clip_grad_norm_ coefficient / DDP averaging).

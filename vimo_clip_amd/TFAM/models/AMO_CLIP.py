@@ -202,6 +202,9 @@ class AMO_CLIP(nn.Module):
         self.projection_layer = _linear_init(_Lin(2 * d_model, d_model))
         self.fused_inference = True     # eval + no_grad forwards of short clips run the fused launch chain (tfam_fused.py)
         self.fused_training = True      # train-mode forwards of short clips run the fused training chains (tfam_train.py)
+        # ... the feature concatenation (use_cross_attention=False, concat_dim=-1) too, with projection_layer inside the chains; only
+        # together with fused_training.  Off: that mode trains on the per-op path, as it always has.
+        self.fused_feature_training = False
         self.set_dropout_seed(0x5EED)
 
     def set_dropout_seed(self, seed: int):
@@ -274,8 +277,14 @@ class AMO_CLIP(nn.Module):
                     x = torch.cat([rgb_cut, motion_emb], dim=1)               # token concat: memory plumbing
                     m = torch.cat([m_cut, m_flow], dim=1).contiguous() if m_cut is not None else None
             else:
-                if training:                          # the projection layer's gradient needs d(tokens): per-op path
-                    return None
+                if training:
+                    if not self.fused_feature_training:      # the projection layer's gradient needs d(tokens): per-op path
+                        return None
+                    # the chains that start at the projection take the concatenated features themselves (tfam_train.forward_train(proj=True))
+                    xcat = concat[0] if concat is not None else torch.cat([rgb_cut, motion_emb], dim=-1)
+                    if xcat.shape[-1] != 2 * self.d_model or not tt.supported_proj(self, xcat.shape[0], xcat.shape[1]):
+                        return None
+                    return _f32c(xcat), m_flow, None, None, False
                 xcat = concat[0] if concat is not None else torch.cat([rgb_cut, motion_emb], dim=-1)
                 if not tf.supported(self, xcat.shape[0], xcat.shape[1], 0, False):
                     return None
@@ -306,6 +315,8 @@ class AMO_CLIP(nn.Module):
         if sel is None:
             return None
         x, m, motion, m_kv, cross = sel
+        if x.shape[-1] != self.d_model:               # the feature concatenation [B, T, 2 d_model] (fused_feature_training)
+            return tt.forward_train(self, x, motion, m, m_kv, cross, self._next_seed, pool_len=pool_len, proj=True)
         return tt.forward_train(self, x, motion, m, m_kv, cross, self._next_seed, pool_len=pool_len)
 
     @property

@@ -41,6 +41,7 @@ class Config:
         self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
         self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
         self.device_metrics = False  # log logits / labels / loss on the device inside the step, read once per epoch (metrics.DeviceMetricLog)
+        self.fused_feature_training = False  # the feature concatenation (concat_dim = -1) trains on the fused chains too (AMO_CLIP.fused_feature_training)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
 
@@ -76,6 +77,8 @@ class Config:
             kw["device_store"] = bool(t["device_store"])
         if "device_metrics" in t:                   # optional as well
             kw["device_metrics"] = bool(t["device_metrics"])
+        if "fused_feature_training" in t:           # optional as well
+            kw["fused_feature_training"] = bool(t["fused_feature_training"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -260,6 +263,8 @@ class ModelTrainer:
         self.scheduler = CosineAnnealingLR(self.optimizer, T_max=config.epochs, eta_min=1e-6)
         self.reducer = parallel.GradientAllReducer(self.arena.flat_grad).attach(self.arena)   # buckets go out during the backward
         self.grad_clip_norm = getattr(config, "grad_clip_norm", None)
+        if hasattr(model, "fused_feature_training"):   # the trainer's configuration decides (off by default)
+            model.fused_feature_training = bool(getattr(config, "fused_feature_training", False))
         bucket = int(getattr(config, "graph_bucket", 1))
         bucket_concat = bool(getattr(config, "graph_bucket_concat", False))
         self._graphed_eval = (GraphedEvalForward(model, config, bucket=bucket, concat_bucket=bucket_concat)
@@ -587,10 +592,12 @@ def _labels_from_annotations(path, num_classes, limit=None):
 
 def build_model(cfg):
     """AMO_CLIP(...) exactly as :379-393 builds it from the config."""
-    return AMO_CLIP(d_model=cfg.d_model, nhead=cfg.nhead, num_layers=cfg.num_layers, dim_feedforward=cfg.dim_feedforward,
-                    num_classes=cfg.num_classes, use_only_rgb=cfg.use_only_rgb, use_only_flow=cfg.use_only_flow, use_pe=cfg.use_pe,
-                    use_cross_attention=cfg.use_cross_attention, concat_dim=cfg.concat_dim, dropout=cfg.dropout,
-                    mlp_dropout=cfg.mlp_dropout, device=cfg.device).to(cfg.device)
+    model = AMO_CLIP(d_model=cfg.d_model, nhead=cfg.nhead, num_layers=cfg.num_layers, dim_feedforward=cfg.dim_feedforward,
+                     num_classes=cfg.num_classes, use_only_rgb=cfg.use_only_rgb, use_only_flow=cfg.use_only_flow, use_pe=cfg.use_pe,
+                     use_cross_attention=cfg.use_cross_attention, concat_dim=cfg.concat_dim, dropout=cfg.dropout,
+                     mlp_dropout=cfg.mlp_dropout, device=cfg.device).to(cfg.device)
+    model.fused_feature_training = bool(getattr(cfg, "fused_feature_training", False))
+    return model
 
 
 def build_datasets(cfg, limit=2048, train_annotations=None, val_annotations=None):
@@ -662,6 +669,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
     ap.add_argument("--device-store", action="store_true", help="hold the embedding sets in device memory and assemble batches there")
     ap.add_argument("--graph-bucket-concat", action="store_true",
                     help="with use_graphs and graph_bucket > 1: bucket the two concatenation modes as well")
+    ap.add_argument("--fused-feature-training", action="store_true",
+                    help="feature concatenation (concat_dim = -1): train on the fused chains, projection layer included")
     ap.add_argument("--device-metrics", action="store_true", help="log loss and metric inputs on the device inside the step, read once per epoch")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
@@ -674,6 +683,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
         over["device_metrics"] = True
     if args.graph_bucket_concat:
         over["graph_bucket_concat"] = True
+    if args.fused_feature_training:
+        over["fused_feature_training"] = True
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

@@ -104,6 +104,12 @@ SIGNATURES = {
     "vmc_tfam_train_bwd": (I, [P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, I, P]),
     "vmc_tfam_train_fwd_len": (I, [P, P, P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, P, I, P]),
     "vmc_tfam_train_bwd_len": (I, [P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, P, I, P]),
+    "vmc_tfam_proj_supported": (I, [I] * 7),
+    "vmc_tfam_train_proj_workspace_bytes": (Z, [I] * 7),
+    "vmc_tfam_train_proj_dx0_offset": (ctypes.c_longlong, [I] * 7),
+    "vmc_tfam_train_fwd_proj": (I, [P, P, P, P, P, P, P, Z] + [I] * 7 + [F, F, P, P, I, P]),
+    "vmc_tfam_train_bwd_proj": (I, [P, P, P, P, P, P, Z] + [I] * 7 + [F, F, P, P, I, P]),
+    "vmc_tfam_layer0_bwd_proj": (I, [P, P, P, P, Z] + [I] * 7 + [F, P, I, P]),
     "vmc_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, I, F, P]),
     "vmc_train_tick": (I, [P, P, F, F, I, P]),
     "vmc_adam_step_dev": (I, [P, P, P, P, Z, P, F, F, F, F, I, P]),

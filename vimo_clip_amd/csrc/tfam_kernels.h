@@ -57,6 +57,7 @@ struct TfArgs {
   float* dyout;             // PRO_LNBWD: d(pre-norm sum) fp32 [M, K] (this block's BN columns): the residual path's gradient
   uint16_t* d16out;         // PRO_LNBWD: masked branch gradient, 16-bit [M, K] (the weight gradient's dY)
   float* stats;             // PRO_LNBWD: [M, 2] mean, rstd of the rows of y (n tile 0 writes them; LayerNorm parameter gradients)
+  uint16_t* y16out;         // EPI_RESID32: 16-bit copy of `out` [M, N] (layer 0's dx0 in the feature mode: the projection gradient's dY)
 };
 
 __device__ __forceinline__ int swz16(int chunk, int row) { return chunk ^ (row & 15); }
@@ -583,7 +584,9 @@ __device__ __forceinline__ void tf_epilogue_train(const TfArgs& a, int grow, int
       }
     }
     if (a.keep_out != nullptr) *(uint32_t*)(a.keep_out + e0) = keep;
-    *(float4*)((float*)a.out + (size_t)grow * a.ldo + col) = make_float4(v[0] + rr.x, v[1] + rr.y, v[2] + rr.z, v[3] + rr.w);
+    const float4 y = make_float4(v[0] + rr.x, v[1] + rr.y, v[2] + rr.z, v[3] + rr.w);
+    *(float4*)((float*)a.out + (size_t)grow * a.ldo + col) = y;
+    if (a.y16out != nullptr) *(uint2*)(a.y16out + e0) = make_uint2(pack2<T>(y.x, y.y), pack2<T>(y.z, y.w));
   } else {
     *(float4*)((float*)a.out + (size_t)grow * a.ldo + col) = make_float4(v[0], v[1], v[2], v[3]);
   }
@@ -1012,6 +1015,18 @@ int tf_run_single(TfArgs& a, const TfamPlan& p, hipStream_t s) {
     case 512: return tf_run_bn<T, PRO, EPI, 512, TR>(a, p, s);
     case 384: if constexpr (PRO == PRO_16) return tf_run_bn<T, PRO, EPI, 384, TR>(a, p, s); else return VMC_E_SHAPE;
     case 256: if constexpr (PRO == PRO_16) return tf_run_bn<T, PRO, EPI, 256, TR>(a, p, s); else return VMC_E_SHAPE;
+    default: return VMC_E_SHAPE;
+  }
+}
+
+// F0 of the feature-concatenation mode (kTfamProjInsts): x32 = 16bit(xcat) Wp^T + bp over K = 2 d_model
+template <typename T>
+int tf_run_proj(TfArgs& a, const TfamPlan& p, hipStream_t s) {
+  if (p.rc) return p.rc;
+  if (p.bn != 16 || p.pro != PRO_F32 || p.epi != EPI_BIAS32) return VMC_E_SHAPE;
+  switch (p.kd) {
+    case 1536: return tf_launch<T, 16, PRO_F32, EPI_BIAS32, 1536, 64, 1, 1, true>(a, p, s);
+    case 1024: return tf_launch<T, 16, PRO_F32, EPI_BIAS32, 1024, 64, 1, 1, true>(a, p, s);
     default: return VMC_E_SHAPE;
   }
 }

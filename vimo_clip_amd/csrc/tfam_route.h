@@ -44,6 +44,7 @@ TFAM_HD size_t tf_frag_elems(int clips, int H, int DH, int NTT = 2) { return (si
 
 struct TfDims {
   int B, T, Tk, D, H, ff, L, C, has_cross;
+  int proj = 0;      // feature-concatenation mode: the chain starts at projection_layer (the section at the end of this file)
 };
 
 // ---- the builder's A/B switches (environment; read once per process by tfam_train.hip) ---------------------------------------
@@ -642,3 +643,87 @@ static inline long long tfam_train_pool_grad_offset(const TfDims& d) {
   const TrWs ws = tr_ws(nullptr, d);
   return (long long)(uintptr_t)tr_lw(ws, d, d.L - 1).dx3;
 }
+
+// ---- feature-concatenation mode: projection_layer in front of layer 0 (training chains) --------------------------------------------
+// AMO_CLIP with use_cross_attention = false, concat_dim = -1 (TFAM/models/AMO_CLIP.py:153-157): x = Linear(2 D, D)(cat(rgb, motion)).
+// The chain's input is the materialised xcat [M, 2 D] fp32.  What it adds to the training chains of a model without cross attention:
+//   F0     x32 = 16bit(xcat) Wp^T + bp   one single-shot launch in front of layer 0 (K = 2 D; side output xcat16), 32-row blocks
+//   L8(0)  dx0 = dy1 + dqkv Wqkv         layer 0 runs the K = 3 D ring that the other layers run, with a 16-bit side output d0_16
+//   one more problem (d0_16^T xcat16 -> projection weight and bias gradient) in the grouped launch that holds layer 0's problems
+// Their kernels live in a table of their own: kTfamInsts lists what the shapes WITHOUT a projection reach.
+constexpr TfamInst kTfamProjInsts[] = {
+    {TFAM_SINGLE, 16, PRO_F32, EPI_BIAS32, 1024, 64, 1, 1, 1, 0, 0, 64 * TF_NW},
+    {TFAM_SINGLE, 16, PRO_F32, EPI_BIAS32, 1536, 64, 1, 1, 1, 0, 0, 64 * TF_NW},
+};
+constexpr int kTfamProjInstCount = sizeof(kTfamProjInsts) / sizeof(kTfamProjInsts[0]);
+static inline int tfam_find_proj_inst(const TfamPlan& p) {
+  for (int i = 0; i < kTfamProjInstCount; ++i) {
+    const TfamInst& k = kTfamProjInsts[i];
+    if (k.family == p.family && k.bn == p.bn && k.pro == p.pro && k.epi == p.epi && k.kd == p.kd && k.dh == p.dh && k.qt == p.qt &&
+        k.nkt == p.nkt && k.tr == p.tr && k.kc == p.kc && k.maxb == p.maxb)
+      return i;
+  }
+  return -1;
+}
+
+// F0.  The 16-column tile is the only one whose A and W images of K = 1536 fit TF_LDS_MAX ((32 + 16) x 1536 x 2 B = 147 456 B).
+static inline TfamPlan tfam_route_proj_fwd(const TfDims& d) {
+  const int K = 2 * d.D, bn = 16, M = d.B * d.T;
+  if (K != 1024 && K != 1536) return tfam_error(VMC_E_SHAPE);      // the instantiated K
+  const size_t lds = tfam_lds_bytes(bn, false, K, 1, 1, 0);
+  if (lds > TF_LDS_MAX) return tfam_error(VMC_E_SHAPE);
+  if ((TF_NW / 2 - 1) * 2 * (bn / 16) * 1024 > TF_BM * K * 2) return tfam_error(VMC_E_SHAPE);
+  TfamPlan p;
+  p.family = TFAM_SINGLE;
+  p.bn = bn; p.pro = PRO_F32; p.epi = EPI_BIAS32; p.kd = K; p.dh = 64; p.qt = 1; p.nkt = 1; p.tr = 1;
+  p.n_tiles = d.D / bn;
+  p.n_rb = (M + TF_BM - 1) / TF_BM;
+  p.grid = (unsigned)(p.n_tiles * p.n_rb);
+  p.block = 64 * TF_NW;
+  p.lds = (int)lds;
+  return p;
+}
+// L8 of layer 0
+static inline TfamPlan tfam_route_proj_bwd(const TfDims& d, const TfamBlocks& b) { return tfam_plan_ring(b.M, d.D, 3 * d.D, b.rpb, true); }
+// the grouped launch that holds layer 0's problems (`layers` deferred layers) with the projection's problem behind them
+static inline TfamPlan tfam_route_proj_wgrad(const TfDims& d, int layers) {
+  TfamPlan p = tfam_route_wgrad(d, layers);
+  if (p.rc) return p;
+  if (layers * tfam_wgrad_layer(d).nprob + 1 > TR_MAX_PROB) return tfam_error(VMC_E_SHAPE);
+  p.grid += (unsigned)tfam_tn_tiles(d.D, 2 * d.D);
+  return p;
+}
+// The supported set: tfam_check(train), and 12 no cross attention, 13 an instantiated K = 2 d_model whose tile fits TF_LDS_MAX,
+// 14 L nprob + 1 <= TR_MAX_PROB: every layer's problems and the projection's fit one table (L <= 7 at four problems per layer).
+static inline int tfam_check_proj(const TfDims& d) {
+  if (int rc = tfam_check(d, true)) return rc;
+  if (d.has_cross) return VMC_E_SHAPE;
+  if (int rc = tfam_route_proj_fwd(d).rc) return rc;
+  if (d.L * tfam_wgrad_layer(d).nprob + 1 > TR_MAX_PROB) return VMC_E_SHAPE;
+  return 0;
+}
+
+// Workspace extension, laid out BEHIND the training workspace (every offset of tr_ws stays what it is without a projection).
+struct TrProjWs {
+  float* x32;               // [M, D]   projection output: layer 0's tokens (the residual operand of its F2)
+  uint16_t* xcat16;         // [M, 2D]  16-bit cast of the concatenated features: the X operand of the projection's weight gradient
+  float* dx0;               // [M, D]   gradient wrt x32
+  uint16_t* d0_16;          // [M, D]   its 16-bit copy: the dY operand
+  size_t bytes;             // of the whole workspace, tr_ws included
+};
+static inline TrProjWs tr_proj_ws(void* base, const TfDims& d) {
+  const size_t M = (size_t)d.B * d.T, D = d.D;
+  char* p = (char*)base;
+  TrProjWs w;
+  size_t o = tr_ws(nullptr, d).bytes;
+  auto take = [&](size_t n) { char* q = p + o; o += tr_al(n); return q; };
+  w.x32 = (float*)take(M * D * 4);
+  w.xcat16 = (uint16_t*)take(M * 2 * D * 2);
+  w.dx0 = (float*)take(M * D * 4);
+  w.d0_16 = (uint16_t*)take(M * D * 2);
+  w.bytes = o;
+  return w;
+}
+static inline size_t tfam_train_proj_workspace_bytes(const TfDims& d) { return tr_proj_ws(nullptr, d).bytes; }
+// offset of dx0 (rows behind the pool length are exactly zero there)
+static inline long long tfam_train_proj_dx0_offset(const TfDims& d) { return (long long)(uintptr_t)tr_proj_ws(nullptr, d).dx0; }

@@ -18,6 +18,9 @@
 //   L6 dOs  = [LNbwd_self(dx1) . keep1] Wo_s
 //   L7 dqkv = attention backward
 //   L8 dx0  = dy1 + dqkv Wqkv        (= dx3 of the layer below; skipped for layer 0)           (K = 3D ring)
+// Feature-concatenation mode (the _proj entries; tfam_route.h, last section): F0 x32 = 16bit(xcat) Wp^T + bp in front of layer 0, whose
+// F1 / F2 read x32 as their tokens; L8 runs for layer 0 too (dx0 and its 16-bit copy into the workspace extension), and the projection's
+// weight / bias gradient d0_16^T xcat16 is one more problem of the grouped launch that holds layer 0's.
 // and ONE grouped launch (tr_wgrad_group_kernel) for the seven weight gradients dW = dY^T X (contraction over the <= 256
 // token rows: the TN body of gemm_tn.hip, one 256 x 128 tile per workgroup), their bias gradients (ones-MFMA on the dY
 // fragments) and the three LayerNorms' gamma / beta gradients.
@@ -471,7 +474,8 @@ int tr_wgrad_launch(const TrWgradGroup& g, hipStream_t s) {
 // all layers' problems once, after the last dgrad chain: one HBM-write-bound launch instead of four with a tail each)
 template <typename T>
 int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, const TfDims& d, const TrWs& ws,
-                 float p, const uint64_t* seeds, int dtype16, hipStream_t s, TrWgradGroup* defer = nullptr) {
+                 float p, const uint64_t* seeds, int dtype16, hipStream_t s, TrWgradGroup* defer = nullptr, const TrProjWs* pw = nullptr,
+                 const vmc_tfam_proj_params* pp = nullptr) {
   const TfamBlocks bk = tfam_blocks(d);
   const TfamStep<TFAM_B_COUNT> plan = tfam_route_layer_bwd(d, bk, layer == 0, tr_overrides());
   if (plan.rc) return plan.rc;
@@ -541,14 +545,16 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
                               d.B, d.H, d.T, d.T, dh, 3 * D, 3 * D, 3 * D, D, 3 * D, 3 * D, 3 * D, drop ? p : 0.f, drop ? seeds[0] : 0, w.attn_ws, aws,
                               dtype16, s)))
     return rc;
-  if (layer > 0) {  // L8: dx3 of the layer below = dy1 + dqkv Wqkv
-    const TrLayerWs wp = tr_lw(ws, d, layer - 1);
+  const bool proj = layer == 0 && pw != nullptr;      // feature mode: layer 0's input is the projection's output, which needs its gradient
+  if (layer > 0 || proj) {  // L8: dx3 of the layer below (dx0 of the projection) = dy1 + dqkv Wqkv
     TfArgs a = {};
     a.M = M; a.N = D; a.K = 3 * D; a.rpb = rpb;
     a.A = w.dqkv16; a.lda = 3 * D;
     a.W = (const uint16_t*)P.wt_self_in; a.ldw = 3 * D;
-    a.resid = w.dy1; a.ldres = D; a.out = wp.dx3; a.ldo = D;
-    if ((rc = tf_run_ring<T, true>(a, plan.p[TFAM_B_DX0], s))) return rc;
+    a.resid = w.dy1; a.ldres = D; a.ldo = D;
+    if (proj) { a.out = pw->dx0; a.y16out = pw->d0_16; }
+    else a.out = tr_lw(ws, d, layer - 1).dx3;
+    if ((rc = tf_run_ring<T, true>(a, proj ? tfam_route_proj_bwd(d, bk) : plan.p[TFAM_B_DX0], s))) return rc;
   }
   // weight, bias and LayerNorm-parameter gradients: one grouped launch
   TrWgradGroup local = {};
@@ -567,6 +573,7 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
   tr_add_ln(g, w.dx3, w.y3, w.st3, P.g_ln_ffn_g, P.g_ln_ffn_b);
   if (d.has_cross) tr_add_ln(g, w.dx2, w.y2, w.st2, P.g_ln_cross_g, P.g_ln_cross_b);
   tr_add_ln(g, dx_self, w.y1, w.st1, P.g_ln_self_g, P.g_ln_self_b);
+  if (proj) tr_add_prob(g, pw->d0_16, pw->xcat16, pp->gw_proj, pp->gb_proj, M, D, 2 * D, D, 2 * D);
   return defer ? 0 : tr_wgrad_launch<T>(g, s);
 }
 
@@ -696,4 +703,94 @@ extern "C" int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, con
                                   int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds, int dtype16, void* stream) {
   return vmc_tfam_train_bwd_len(dlogits, mask, mask_kv, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_drop, p_mlp,
                                 seeds, nullptr, dtype16, stream);
+}
+
+// ---- feature-concatenation mode: the chains with projection_layer in front of layer 0 -------------------------------------------------
+namespace {
+
+// F0: x32 = 16bit(xcat) Wp^T + bp, xcat16 saved
+template <typename T>
+int tr_proj_fwd(const float* xcat, const vmc_tfam_proj_params& pp, const TfDims& d, const TrProjWs& pw, hipStream_t s) {
+  const TfamPlan plan = tfam_route_proj_fwd(d);
+  TfArgs a = {};
+  a.M = d.B * d.T; a.N = d.D; a.K = 2 * d.D; a.rpb = TF_BM;
+  a.A = xcat; a.lda = 2 * d.D;
+  a.W = (const uint16_t*)pp.w_proj; a.ldw = 2 * d.D; a.bias = pp.b_proj;
+  a.out = pw.x32; a.ldo = d.D;
+  a.x16out = pw.xcat16;
+  return tf_run_proj<T>(a, plan, s);
+}
+
+}  // namespace
+
+#define TR_PROJ_PROLOG()                                                                      \
+  TfDims d = {B, T, 0, D, H, ff, L, C, 0, 1};                                                 \
+  if (int rc_ = tfam_check_proj(d)) return rc_;                                               \
+  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;                          \
+  const TrWs ws = tr_ws(workspace, d);                                                        \
+  const TrProjWs pw = tr_proj_ws(workspace, d);                                               \
+  if (workspace == nullptr || workspace_bytes < pw.bytes || (((uintptr_t)workspace) & 255)) return VMC_E_ARG; \
+  hipStream_t s = (hipStream_t)stream
+
+extern "C" int vmc_tfam_proj_supported(int B, int T, int D, int H, int ff, int L, int C) {
+  TfDims d = {B, T, 0, D, H, ff, L, C, 0, 1};
+  return tfam_check_proj(d);
+}
+extern "C" size_t vmc_tfam_train_proj_workspace_bytes(int B, int T, int D, int H, int ff, int L, int C) {
+  TfDims d = {B, T, 0, D, H, ff, L, C, 0, 1};
+  if (tfam_check_proj(d)) return 0;
+  return tfam_train_proj_workspace_bytes(d);
+}
+extern "C" long long vmc_tfam_train_proj_dx0_offset(int B, int T, int D, int H, int ff, int L, int C) {
+  TfDims d = {B, T, 0, D, H, ff, L, C, 0, 1};
+  if (tfam_check_proj(d)) return -1;
+  return tfam_train_proj_dx0_offset(d);
+}
+
+extern "C" int vmc_tfam_train_fwd_proj(const float* xcat, const vmc_tfam_proj_params* proj, const uint8_t* mask, const vmc_tfam_layer_params* layers,
+                                       const vmc_tfam_head_params* head, float* logits, void* workspace, size_t workspace_bytes, int B, int T, int D,
+                                       int H, int ff, int L, int C, float p_drop, float p_mlp, const uint64_t* seeds, const int* pool_len,
+                                       int dtype16, void* stream) {
+  if (!xcat || !proj || !proj->w_proj || !proj->b_proj || !layers || !head || !logits) return VMC_E_ARG;
+  TR_PROJ_PROLOG();
+  (void)ws;
+  if (int rc = dtype16 == VMC_BF16 ? tr_proj_fwd<BF16>(xcat, *proj, d, pw, s) : tr_proj_fwd<F16>(xcat, *proj, d, pw, s)) return rc;
+  return vmc_tfam_train_fwd_len(pw.x32, nullptr, mask, nullptr, layers, head, logits, workspace, workspace_bytes, B, T, 0, D, H, ff, L, C, 0, p_drop,
+                                p_mlp, seeds, pool_len, dtype16, stream);
+}
+
+extern "C" int vmc_tfam_layer0_bwd_proj(const vmc_tfam_proj_params* proj, const uint8_t* mask, const vmc_tfam_layer_params* layers, void* workspace,
+                                        size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop, const uint64_t* seeds,
+                                        int dtype16, void* stream) {
+  TR_PROJ_PROLOG();
+  if (!proj || !layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
+  return dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, nullptr, layers, 0, d, ws, p_drop, seeds, dtype16, s, nullptr, &pw, proj)
+                             : tr_layer_bwd<F16>(mask, nullptr, layers, 0, d, ws, p_drop, seeds, dtype16, s, nullptr, &pw, proj);
+}
+
+extern "C" int vmc_tfam_train_bwd_proj(const float* dlogits, const vmc_tfam_proj_params* proj, const uint8_t* mask, const vmc_tfam_layer_params* layers,
+                                       const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int D, int H, int ff,
+                                       int L, int C, float p_drop, float p_mlp, const uint64_t* seeds, const int* pool_len, int dtype16,
+                                       void* stream) {
+  if (!proj || (p_mlp > 0.f && !seeds)) return VMC_E_ARG;
+  TR_PROJ_PROLOG();
+  if (!layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
+  int rc = vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, 0, D, H, ff, L, C, 0, p_mlp, seeds ? seeds[7 * L] : 0, pool_len,
+                                 dtype16, stream);
+  if (rc) return rc;
+  // as vmc_tfam_train_bwd_len: every dgrad chain, then the weight gradients in one launch per tfam_wgrad_flush; the last one holds
+  // layer 0's problems and the projection's
+  TrWgradGroup g = {};
+  for (int l = L - 1; l >= 0; --l) {
+    const uint64_t* sl = seeds ? seeds + 7 * l : nullptr;
+    rc = dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, nullptr, layers, l, d, ws, p_drop, sl, dtype16, s, &g, &pw, proj)
+                             : tr_layer_bwd<F16>(mask, nullptr, layers, l, d, ws, p_drop, sl, dtype16, s, &g, &pw, proj);
+    if (rc) return rc;
+    if (tfam_wgrad_flush(L, l)) {
+      rc = dtype16 == VMC_BF16 ? tr_wgrad_launch<BF16>(g, s) : tr_wgrad_launch<F16>(g, s);
+      if (rc) return rc;
+      g = TrWgradGroup{};
+    }
+  }
+  return 0;
 }

@@ -8,6 +8,10 @@ compute copies (and their transposes) that ``autograd_ops.weights`` keeps curren
 masters of biases / LayerNorm parameters, and write gradients straight into the parameters' gradient slots (the flat arena
 of optim.GradArena when there is one).  Dropout draws the same seeds, in the same order, with the same element indices as
 the per-op path (AttentionLayer.run), so both paths apply identical masks.
+
+The feature concatenation (use_cross_attention=False, concat_dim=-1; AMO_CLIP.fused_feature_training) takes the ``_proj`` entries:
+the chain starts at projection_layer, one launch in front of layer 0, and the projection's gradients come out of the grouped
+weight-gradient launch that holds layer 0's (``forward_train(..., proj=True)`` with the concatenated features as ``x``).
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ _LAYER_FIELDS = (
     "g_ln_self_g g_ln_self_b g_ln_cross_g g_ln_cross_b g_ln_ffn_g g_ln_ffn_b").split()
 _HEAD_FIELDS = ("w_cls1 w_cls4 w32_cls1 w32_cls4 cls_ln_g cls_ln_b b_cls1 b_cls4 "
                 "g_cls_ln_g g_cls_ln_b gw_cls1 gb_cls1 gw_cls4 gb_cls4").split()
+_PROJ_FIELDS = "w_proj b_proj gw_proj gb_proj".split()
 
 
 class LayerParams(ctypes.Structure):          # vmc_tfam_layer_params
@@ -39,6 +44,10 @@ class HeadParams(ctypes.Structure):           # vmc_tfam_head_params
     _fields_ = [(n, ctypes.c_void_p) for n in _HEAD_FIELDS]
 
 
+class ProjParams(ctypes.Structure):           # vmc_tfam_proj_params
+    _fields_ = [(n, ctypes.c_void_p) for n in _PROJ_FIELDS]
+
+
 SEEDS_PER_LAYER = 7
 
 
@@ -46,6 +55,22 @@ def supported(model, B, T, Tk, has_cross) -> bool:
     """Batches that take the training chains: tfam_fused.supported's policy over the shapes vmc_tfam_supported accepts for training
     (the eval chain's set, at most 256 token rows, at most 32 clips, a class count that is a multiple of 4 and at most 480)."""
     return tfam_fused.supported(model, B, T, Tk, has_cross, train=True)
+
+
+def supported_proj(model, B, T) -> bool:
+    """Batches of the feature-concatenation mode (projection_layer in front of layer 0) that take the training chains: the policy of
+    ``supported`` over the shapes vmc_tfam_proj_supported accepts (no cross attention, at most 7 layers)."""
+    if B * T > tfam_fused.MAX_ROWS or model.layers[0].ffn_act != 3:
+        return False
+    key = tfam_fused.dims(model, B, T, 0, False)
+    key = key[:2] + key[3:8]
+    ok = _proj_answers.get(key)
+    if ok is None:
+        ok = _proj_answers[key] = lib.vmc_tfam_proj_supported(*key) == 0
+    return ok
+
+
+_proj_answers = {}
 
 
 def _grad_dst(p, fresh):
@@ -64,8 +89,8 @@ def _grad_dst(p, fresh):
 class _Tables:
     """ctypes arrays of vmc_tfam_layer_params / vmc_tfam_head_params for one (model, compute dtype)."""
 
-    def __init__(self, model, dtype16, cross):
-        self.model, self.dtype16, self.cross = model, dtype16, cross
+    def __init__(self, model, dtype16, cross, proj=False):
+        self.model, self.dtype16, self.cross, self.proj = model, dtype16, cross, proj
         self.key = None
         self.keep = []
 
@@ -80,17 +105,20 @@ class _Tables:
             out += [layer.ffn[0].weight, layer.ffn[0].bias, layer.ffn[3].weight, layer.ffn[3].bias,
                     layer.norm_self.weight, layer.norm_self.bias, layer.norm_ffn.weight, layer.norm_ffn.bias]
         c = m.classifier
-        return out + [c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[4].weight, c[4].bias]
+        out += [c[0].weight, c[0].bias, c[1].weight, c[1].bias, c[4].weight, c[4].bias]
+        if self.proj:
+            out += [m.projection_layer.weight, m.projection_layer.bias]
+        return out
 
     def build(self, fresh=None):
-        """(layers array, head struct).  Cached; rebuilt when a parameter, a compute copy or a gradient slot moved.  fresh: a dict
+        """(layers array, head struct, projection struct or None).  Cached; rebuilt when a parameter, a compute copy or a gradient slot moved.  fresh: a dict
         -> parameters without a gradient slot get new fp32 gradient tensors (collected in it; nothing is cached then)."""
         ps = self.params()
         key = (ag.weights.generation, tuple(p.requires_grad for p in ps),
                tuple((p._version, p.data_ptr(), 0 if getattr(p, "_vmc_grad", None) is None else p._vmc_grad.data_ptr()) for p in ps))
         if fresh is None:
             if key == self.key:
-                return self.layers, self.head
+                return self.layers, self.head, self.projp
             if torch.cuda.is_current_stream_capturing() and self.key is not None:
                 raise RuntimeError("TFAM training chain: parameters or their compute copies moved during a graph capture")
             fresh_d = {}
@@ -154,43 +182,55 @@ class _Tables:
         h.cls_ln_g, h.cls_ln_b, h.b_cls1, h.b_cls4 = f(c[0].weight), f(c[0].bias), f(c[1].bias), f(c[4].bias)
         h.g_cls_ln_g, h.g_cls_ln_b = g(c[0].weight), g(c[0].bias)
         h.gw_cls1, h.gb_cls1, h.gw_cls4, h.gb_cls4 = g(c[1].weight), g(c[1].bias), g(c[4].weight), g(c[4].bias)
+        pp = None
+        if self.proj:                                        # the projection in front of layer 0: no dgrad through it, so no transpose
+            pl, pp = m.projection_layer, ProjParams()
+            keep.append(ag.weights.get(pl.weight, d16))
+            pp.w_proj, pp.b_proj = keep[-1].data_ptr(), f(pl.bias)
+            pp.gw_proj, pp.gb_proj = g(pl.weight), g(pl.bias)
         if fresh is None:
-            self.key, self.layers, self.head, self.keep = key, layers, h, keep
+            self.key, self.layers, self.head, self.projp, self.keep = key, layers, h, pp, keep
         else:
             fresh_d["_keep"] = keep
-        return layers, h
+        return layers, h, pp
 
 
-def _tables(model, dtype16, cross) -> _Tables:
+def _tables(model, dtype16, cross, proj=False) -> _Tables:
     tabs = model.__dict__.setdefault("_tfam_train_tables", {})
-    t = tabs.get((dtype16, cross))
+    t = tabs.get((dtype16, cross, proj))
     if t is None:
-        t = tabs[(dtype16, cross)] = _Tables(model, dtype16, cross)
+        t = tabs[(dtype16, cross, proj)] = _Tables(model, dtype16, cross, proj)
     return t
 
 
 class TfamTrainFn(torch.autograd.Function):
-    """logits = AMO_CLIP(x, motion) in train mode.  Inputs after ``seeds`` are the parameters (so that autograd asks for their
-    gradients); their values are read through the pointer tables, not through these tensors."""
+    """logits = AMO_CLIP(x, motion) in train mode.  Inputs after ``proj`` are the parameters (so that autograd asks for their
+    gradients); their values are read through the pointer tables, not through these tensors.  ``proj``: x is the feature
+    concatenation [B, T, 2 D] and the chain starts at projection_layer (the vmc_tfam_*_proj entries)."""
 
     @staticmethod
-    def forward(ctx, model, x, motion, mask, mask_kv, cross, p_drop, p_mlp, seeds, pool_len, *params):
+    def forward(ctx, model, x, motion, mask, mask_kv, cross, p_drop, p_mlp, seeds, pool_len, proj, *params):
         dt16 = model.compute_dtype
-        B, T, D = x.shape
+        B, T, _ = x.shape
         Tk = motion.shape[1] if cross else 0
         dims = tfam_fused.dims(model, B, T, Tk, cross)
-        tab = _tables(model, dt16, cross)
-        layers, head = tab.build()
-        nbytes = lib.vmc_tfam_train_workspace_bytes(*dims)
+        tab = _tables(model, dt16, cross, proj)
+        layers, head, projp = tab.build()
+        pdims = dims[:2] + dims[3:8]                         # the _proj entries take neither Tk nor has_cross
+        nbytes = lib.vmc_tfam_train_proj_workspace_bytes(*pdims) if proj else lib.vmc_tfam_train_workspace_bytes(*dims)
         if nbytes == 0:
             raise RuntimeError("vmc_tfam_train_workspace_bytes: unsupported shape")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         logits = torch.empty((B, dims[7]), dtype=torch.float32, device=x.device)
         sarr = (ctypes.c_uint64 * len(seeds))(*seeds) if seeds else None
-        check(lib.vmc_tfam_train_fwd_len(ptr(x), ptr(motion) if cross else None, ptr(mask), ptr(mask_kv) if cross else None, layers,
-                                         ctypes.byref(head), ptr(logits), ptr(ws), nbytes, *dims, float(p_drop), float(p_mlp), sarr,
-                                         ptr(pool_len), dt(dt16), stream()), "tfam_train_fwd")
-        ctx.model, ctx.tab, ctx.ws, ctx.dims, ctx.cross = model, tab, ws, dims, cross
+        if proj:
+            check(lib.vmc_tfam_train_fwd_proj(ptr(x), ctypes.byref(projp), ptr(mask), layers, ctypes.byref(head), ptr(logits), ptr(ws), nbytes,
+                                              *pdims, float(p_drop), float(p_mlp), sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_fwd_proj")
+        else:
+            check(lib.vmc_tfam_train_fwd_len(ptr(x), ptr(motion) if cross else None, ptr(mask), ptr(mask_kv) if cross else None, layers,
+                                             ctypes.byref(head), ptr(logits), ptr(ws), nbytes, *dims, float(p_drop), float(p_mlp), sarr,
+                                             ptr(pool_len), dt(dt16), stream()), "tfam_train_fwd")
+        ctx.model, ctx.tab, ctx.ws, ctx.dims, ctx.cross, ctx.proj = model, tab, ws, dims, cross, proj
         ctx.masks, ctx.drop, ctx.sarr, ctx.params = (mask, mask_kv), (float(p_drop), float(p_mlp)), sarr, params
         ctx.pool_len = pool_len                              # the backward reads the same device value
         return logits
@@ -207,9 +247,10 @@ class TfamTrainFn(torch.autograd.Function):
         dt16 = model.compute_dtype
         fresh = {}
         need_fresh = any(p.requires_grad and getattr(p, "_vmc_grad", None) is None for p in ctx.params)
-        layers, head = tab.build(fresh) if need_fresh else tab.build()      # slot-less parameters: new gradient tensors, returned below
+        layers, head, projp = tab.build(fresh) if need_fresh else tab.build()      # slot-less parameters: new gradient tensors, returned below
         dlogits = dlogits.contiguous().float()
         L = dims[6]
+        proj, pdims = ctx.proj, dims[:2] + dims[3:8]
         sarr, nbytes = ctx.sarr, ws.numel()
         off = ctypes.sizeof(ctypes.c_uint64)
         seed_at = (lambda i: ctypes.cast(ctypes.addressof(sarr) + i * off, ctypes.c_void_p)) if sarr is not None else (lambda i: None)
@@ -219,8 +260,12 @@ class TfamTrainFn(torch.autograd.Function):
         if not ag.grad_ready_hooks and done is None:
             # nobody waits for a layer's gradients (single process): the whole backward in one call -- the dgrad chains of all layers,
             # then every weight gradient in ONE grouped launch (vmc_tfam_train_bwd)
-            check(lib.vmc_tfam_train_bwd_len(ptr(dlogits), ptr(mask), ptr(mask_kv) if cross else None, layers, ctypes.byref(head), ptr(ws),
-                                             nbytes, *dims, p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_bwd")
+            if proj:
+                check(lib.vmc_tfam_train_bwd_proj(ptr(dlogits), ctypes.byref(projp), ptr(mask), layers, ctypes.byref(head), ptr(ws), nbytes, *pdims,
+                                                  p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_bwd_proj")
+            else:
+                check(lib.vmc_tfam_train_bwd_len(ptr(dlogits), ptr(mask), ptr(mask_kv) if cross else None, layers, ctypes.byref(head), ptr(ws),
+                                                 nbytes, *dims, p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_bwd")
         else:
             check(lib.vmc_tfam_head_bwd_len(ptr(dlogits), layers, ctypes.byref(head), ptr(ws), nbytes, *dims, p_mlp,
                                             int(sarr[SEEDS_PER_LAYER * L]) if sarr is not None else 0, ptr(pool_len), dt(dt16), stream()),
@@ -229,8 +274,12 @@ class TfamTrainFn(torch.autograd.Function):
             if done is not None:                                 # group L = the classifier
                 done(L)
             for l in range(L - 1, -1, -1):
-                check(lib.vmc_tfam_layer_bwd(ptr(mask), ptr(mask_kv) if cross else None, layers, l, ptr(ws), nbytes, *dims, p_drop,
-                                             seed_at(SEEDS_PER_LAYER * l), dt(dt16), stream()), "tfam_layer_bwd")
+                if proj and l == 0:                              # layer 0 with the qkv dgrad and the projection's gradients in its launch
+                    check(lib.vmc_tfam_layer0_bwd_proj(ctypes.byref(projp), ptr(mask), layers, ptr(ws), nbytes, *pdims, p_drop, seed_at(0),
+                                                       dt(dt16), stream()), "tfam_layer0_bwd_proj")
+                else:
+                    check(lib.vmc_tfam_layer_bwd(ptr(mask), ptr(mask_kv) if cross else None, layers, l, ptr(ws), nbytes, *dims, p_drop,
+                                                 seed_at(SEEDS_PER_LAYER * l), dt(dt16), stream()), "tfam_layer_bwd")
                 layer = model.layers[l]
                 sa, ca = layer.self_attn, layer.cross_attn
                 rep = [layer.norm_ffn.weight, layer.norm_ffn.bias, layer.ffn[3].weight, layer.ffn[3].bias, layer.ffn[0].weight, layer.ffn[0].bias]
@@ -238,12 +287,14 @@ class TfamTrainFn(torch.autograd.Function):
                     rep += [layer.norm_cross.weight, layer.norm_cross.bias, ca.out_proj.weight, ca.out_proj.bias, ca.in_proj_weight, ca.in_proj_bias,
                             ca.in_proj_weight, ca.in_proj_bias]
                 rep += [layer.norm_self.weight, layer.norm_self.bias, sa.out_proj.weight, sa.out_proj.bias, sa.in_proj_weight, sa.in_proj_bias]
+                if proj and l == 0:                              # complete with layer 0's: reported before done(0)
+                    rep += [model.projection_layer.weight, model.projection_layer.bias]
                 _report(rep)
                 if done is not None:
                     done(l)
         grads = tuple((fresh.get(id(p)) if p.requires_grad and getattr(p, "_vmc_grad", None) is None else None) for p in ctx.params)
         ctx.ws = None
-        return (None,) * 10 + grads
+        return (None,) * 11 + grads
 
 
 def _report(params):
@@ -254,13 +305,17 @@ def _report(params):
                     hook(p)
 
 
-def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None):
+def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None, proj=False):
     """Train-mode forward of ``model`` through the fused chain (autograd-tracked); None when the shapes are outside its set.
     pool_len: one-element int32 device tensor, the rows of every clip that the mean-pool takes (None: all T); the backward
-    leaves a zero gradient on the other rows."""
+    leaves a zero gradient on the other rows.  proj: ``x`` is the feature concatenation xcat [B, T, 2 d_model] fp32 and the
+    chain runs projection_layer in front of layer 0 (no cross attention; the projection draws no seed)."""
     B, T, _ = x.shape
     Tk = motion.shape[1] if cross else 0
-    if x.requires_grad or (cross and motion.requires_grad) or not supported(model, B, T, Tk, cross):
+    if proj:
+        if cross or x.requires_grad or x.shape[-1] != 2 * model.d_model or not supported_proj(model, B, T):
+            return None
+    elif x.requires_grad or (cross and motion.requires_grad) or not supported(model, B, T, Tk, cross):
         return None
     p = float(model.layers[0].p)
     if any(float(layer.p) != p for layer in model.layers):
@@ -280,5 +335,5 @@ def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None
                 row[4], row[5], row[6] = seed_fn(), seed_fn(), seed_fn()
             seeds += row
         seeds.append(seed_fn() if p_mlp > 0.0 else 0)
-    tab = _tables(model, model.compute_dtype, cross)
-    return TfamTrainFn.apply(model, x, motion, mask, mask_kv, cross, p, p_mlp, tuple(seeds), pool_len, *tab.params())
+    tab = _tables(model, model.compute_dtype, cross, proj)
+    return TfamTrainFn.apply(model, x, motion, mask, mask_kv, cross, p, p_mlp, tuple(seeds), pool_len, bool(proj), *tab.params())
