@@ -634,6 +634,58 @@ int vmc_tfam_layer0_bwd_proj(const vmc_tfam_proj_params* proj, const uint8_t* ma
                              const uint64_t* seeds, int dtype16, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * K11-K14 fused, TRAINING, gradients wrt the INPUT TOKENS — for callers whose tokens come out of trainable modules (an adapter in
+ * front of TFAM, learned prompt tokens, end-to-end fine-tuning) or who want per-frame saliency.  The forward entries above run
+ * unchanged on a LARGER workspace (vmc_tfam_train_input_workspace_bytes: the training workspace, or with proj = 1 the projection
+ * mode's, plus an extension behind it; every existing offset is unchanged); the backward entries below do what their namesakes do,
+ * bit for bit, and add:
+ *   dX      fp32 [B*T, D]     VMC_TFAM_WANT_DX, no projection: layer 0 runs the qkv dgrad dX = dy1 + dqkv Wqkv of the other layers (+1
+ *                             launch).  The gradient wrt x of vmc_tfam_train_fwd*.
+ *   dMotion fp32 [B*Tk, D]    VMC_TFAM_WANT_DMOTION, cross attention: sum over the layers of dkv_l Wkv_l (Wkv_l = rows D..3D of layer l's
+ *                             cross in_proj_weight), one K = 2D launch behind each layer's cross-attention backward (+L launches).
+ *                             Layer L-1 writes, the layers below add in the order L-2..0 through the launch's fp32 residual operand:
+ *                             one fixed order, so the result repeats bit for bit.  The per-layer entry must therefore be called for
+ *                             the layers in that order, as the per-layer backward is anyway.
+ *   dXcat   fp32 [B*T, 2D]    projection mode (always wanted there): dx0 Wp, one launch behind layer 0's qkv dgrad (+1 launch).  It
+ *                             reads wt_proj, the 16-bit TRANSPOSE [2D, D] of projection_layer.weight, which vmc_tfam_proj_params has
+ *                             no field for (its layout is fixed) and which only these entries need.
+ * Rows t >= *pool_len of every clip, and motion rows that mask_kv masks, come out as exact zeros.  The parameter gradients are those
+ * of the entries above, bit for bit.  16-bit operands, fp32 accumulation, fp32 outputs.
+ * Shapes: vmc_tfam_input_grad_supported == 0: those of the chain it extends (vmc_tfam_supported(train) / vmc_tfam_proj_supported).
+ * The three gradients live in the extension at vmc_tfam_train_input_grad_offsets; they are valid after the backward call until
+ * the workspace is written again.
+ */
+#define VMC_TFAM_WANT_DX 1
+#define VMC_TFAM_WANT_DMOTION 2
+/* proj = 1: the feature-concatenation mode, which has no cross attention (has_cross = 1 with it is VMC_E_SHAPE).  0 when the shape is taken. */
+int vmc_tfam_input_grad_supported(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj);
+/* 0: unsupported shape */
+size_t vmc_tfam_train_input_workspace_bytes(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj);
+/* offsets[0..2] = byte offsets of dX, dMotion, dXcat inside that workspace; -1 for a gradient the configuration does not have. */
+int vmc_tfam_train_input_grad_offsets(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj,
+                                      long long* offsets);
+/* vmc_tfam_train_bwd_len + the gradients named by `want` (VMC_TFAM_WANT_* bits; 0: exactly vmc_tfam_train_bwd_len). */
+int vmc_tfam_train_bwd_inputs_len(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv,
+                                  const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
+                                  size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross,
+                                  float p_drop, float p_mlp, const uint64_t* seeds, const int* pool_len, int want, int dtype16,
+                                  void* stream);
+/* vmc_tfam_layer_bwd + this layer's part of them: dMotion for every layer, dX for layer 0. */
+int vmc_tfam_layer_bwd_inputs(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer,
+                              void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C,
+                              int has_cross, float p_drop, const uint64_t* seeds, int want, int dtype16, void* stream);
+/* vmc_tfam_train_bwd_proj + dXcat */
+int vmc_tfam_train_bwd_inputs_proj(const float* dlogits, const vmc_tfam_proj_params* proj, const void* wt_proj, const uint8_t* mask,
+                                   const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
+                                   size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop,
+                                   float p_mlp, const uint64_t* seeds, const int* pool_len, int dtype16, void* stream);
+/* vmc_tfam_layer0_bwd_proj + dXcat */
+int vmc_tfam_layer0_bwd_proj_inputs(const vmc_tfam_proj_params* proj, const void* wt_proj, const uint8_t* mask,
+                                    const vmc_tfam_layer_params* layers, void* workspace, size_t workspace_bytes, int B, int T,
+                                    int D, int H, int ff, int L, int C, float p_drop, const uint64_t* seeds, int dtype16,
+                                    void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * K15 — fused Adam / AdamW over one flat fp32 buffer (train.py:66; TFAM/train_and_eval.py:53).
  *   decoupled_wd = 1: p *= 1 - lr*wd first (AdamW); 0: g += wd*p (Adam L2).
  *   grad_scale multiplies g first (clip_grad_norm_ coefficient / DDP averaging).
@@ -771,6 +823,14 @@ int vmc_metric_append(const vmc_metric_log* log, const float* values /* [B, C] *
 int vmc_concat_tokens_len(const float* rgb, const float* motion, const uint8_t* mask_rgb /* [B, T_rgb] or NULL */,
                           const uint8_t* mask_motion /* [B, T_motion] or NULL */, float* x, uint8_t* mask, int* pool_len, int B,
                           int T_rgb, int T_motion, int T_out, int D, const int* len_rgb, const int* len_motion, void* stream);
+/* Its backward: the scatter of dx [B, T_out, D] fp32 to the two streams, lengths read from device memory and clamped as above.
+ *   drgb    [B, T_rgb, D]:    dx[b, t] for t < keep, 0 on every other row (the dropped last RGB row and the padding included)
+ *   dmotion [B, T_motion, D]: dx[b, keep + t] for t < nm, 0 on the rows behind them
+ * Exact copies; every element of both outputs is written on every call, by one pass of plain vector stores (each output row has
+ * one source row or none: no atomics).  Rows n..T_out-1 of dx are not read.  Only enqueues; safe under capture.
+ * VMC_E_ARG: dx / drgb / dmotion NULL.  VMC_E_SHAPE: as the forward. */
+int vmc_concat_tokens_len_bwd(const float* dx, float* drgb, float* dmotion, int B, int T_rgb, int T_motion, int T_out, int D,
+                              const int* len_rgb, const int* len_motion, void* stream);
 
 #ifdef __cplusplus
 }

@@ -205,6 +205,10 @@ class AMO_CLIP(nn.Module):
         # ... the feature concatenation (use_cross_attention=False, concat_dim=-1) too, with projection_layer inside the chains; only
         # together with fused_training.  Off: that mode trains on the per-op path, as it always has.
         self.fused_feature_training = False
+        # ... and the gradients wrt the token tensors (an adapter in front of TFAM, learned tokens, saliency): with this on, tokens that
+        # require grad stay on the fused chains, which then return d rgb / d motion (tfam_train.py), and forward(token_lens=...) takes
+        # them too (the concatenation kernel's backward).  Off: such a step runs per-op, and token_lens raises, as they always have.
+        self.fused_input_grads = False
         self.set_dropout_seed(0x5EED)
 
     def set_dropout_seed(self, seed: int):
@@ -348,7 +352,9 @@ class AMO_CLIP(nn.Module):
                            the motion mask, pooled over n_motion rows: the RGB row the reference drops lands at row n_motion,
                            which is masked and not pooled.  ``mask_flow`` is required.
         Rows 0..n-1 are the reference's concatenation at the batch's own lengths; the rows behind them are masked as keys, stay
-        out of the pool and receive a zero gradient.  The token tensors must not require grad (the kernel has no backward)."""
+        out of the pool and receive a zero gradient.  The token tensors must not require grad (the kernel has no backward) unless
+        ``fused_input_grads`` is on: the concatenation then is an autograd node (vmc_concat_tokens_len_bwd), and the rows behind each
+        stream's own length, the dropped RGB row included, receive an exactly zero gradient."""
         dt16, D = self.compute_dtype, self.d_model
         dev = self.device
         if token_lens is not None:
@@ -357,7 +363,7 @@ class AMO_CLIP(nn.Module):
                                  "use_only_rgb / use_only_flow); the other modes take pool_len")
             if pool_len is not None:
                 raise ValueError("token_lens and pool_len exclude each other: the pool length follows from token_lens")
-            if rgb_emb.requires_grad or motion_emb.requires_grad:
+            if (rgb_emb.requires_grad or motion_emb.requires_grad) and not self.fused_input_grads:
                 raise ValueError("token_lens: the token tensors must not require grad (the concatenation kernel has no backward)")
             if self.concat_dim != 1 and mask_flow is None:
                 raise ValueError("token_lens with concat_dim = -1 needs mask_flow: the padded rows would be attended to")
@@ -386,7 +392,8 @@ class AMO_CLIP(nn.Module):
         if token_lens is not None:                        # after the positional encoding: the rows keep their own stream's phase
             if self.concat_dim == 1:
                 T_out = int(concat_len) if concat_len is not None else rgb_emb.shape[1] - 1 + motion_emb.shape[1]
-                xc, mc, pool_len = ops.concat_tokens(_f32c(rgb_emb), _f32c(motion_emb), m_rgb, m_flow, T_out, *token_lens)
+                cat = ag.concat_tokens if (rgb_emb.requires_grad or motion_emb.requires_grad) else ops.concat_tokens
+                xc, mc, pool_len = cat(_f32c(rgb_emb), _f32c(motion_emb), m_rgb, m_flow, T_out, *token_lens)
                 concat = (xc, mc)
             else:
                 concat = (torch.cat([rgb_emb[:, :motion_emb.shape[1], :], motion_emb], dim=-1), m_flow)

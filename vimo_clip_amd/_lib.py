@@ -110,6 +110,13 @@ SIGNATURES = {
     "vmc_tfam_train_fwd_proj": (I, [P, P, P, P, P, P, P, Z] + [I] * 7 + [F, F, P, P, I, P]),
     "vmc_tfam_train_bwd_proj": (I, [P, P, P, P, P, P, Z] + [I] * 7 + [F, F, P, P, I, P]),
     "vmc_tfam_layer0_bwd_proj": (I, [P, P, P, P, Z] + [I] * 7 + [F, P, I, P]),
+    "vmc_tfam_input_grad_supported": (I, [I] * 10),
+    "vmc_tfam_train_input_workspace_bytes": (Z, [I] * 10),
+    "vmc_tfam_train_input_grad_offsets": (I, [I] * 10 + [P]),
+    "vmc_tfam_train_bwd_inputs_len": (I, [P, P, P, P, P, P, Z] + [I] * 9 + [F, F, P, P, I, I, P]),
+    "vmc_tfam_layer_bwd_inputs": (I, [P, P, P, I, P, Z] + [I] * 9 + [F, P, I, I, P]),
+    "vmc_tfam_train_bwd_inputs_proj": (I, [P, P, P, P, P, P, P, Z] + [I] * 7 + [F, F, P, P, I, P]),
+    "vmc_tfam_layer0_bwd_proj_inputs": (I, [P, P, P, P, P, Z] + [I] * 7 + [F, P, I, P]),
     "vmc_adam_step": (I, [P, P, P, P, Z, F, F, F, F, F, I, I, F, P]),
     "vmc_train_tick": (I, [P, P, F, F, I, P]),
     "vmc_adam_step_dev": (I, [P, P, P, P, Z, P, F, F, F, F, I, P]),
@@ -121,6 +128,7 @@ SIGNATURES = {
     "vmc_gather_clips": (I, [P, I, P, I, ctypes.c_longlong, I, P, P, I, P, P]),
     "vmc_metric_append": (I, [P, P, P, P, I, P]),
     "vmc_concat_tokens_len": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P]),
+    "vmc_concat_tokens_len_bwd": (I, [P, P, P, I, I, I, I, I, P, P, P]),
 }
 
 

@@ -696,3 +696,25 @@ def scale_by_device_scalar(x: torch.Tensor, scalar: torch.Tensor) -> torch.Tenso
     s = scalar.reshape(1).float().contiguous()
     check(lib.vmc_scale_by_device_scalar(ptr(x), ptr(y), x.numel(), ptr(s), stream()), "scale_by_device_scalar")
     return y
+
+
+class ConcatTokensFn(torch.autograd.Function):
+    """ops.concat_tokens with its backward (vmc_concat_tokens_len / _bwd): the token concatenation at device-resident lengths for token
+    tensors that require grad.  The mask and the pool length carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, rgb, motion, mask_rgb, mask_motion, T_out, len_rgb, len_motion):
+        x, mask, pool_len = ops.concat_tokens(rgb, motion, mask_rgb, mask_motion, T_out, len_rgb, len_motion)
+        ctx.meta = (rgb.shape[1], motion.shape[1], len_rgb, len_motion)
+        ctx.mark_non_differentiable(mask, pool_len)
+        return x, mask, pool_len
+
+    @staticmethod
+    def backward(ctx, dx, _dmask, _dlen):
+        T_rgb, T_motion, len_rgb, len_motion = ctx.meta
+        drgb, dmotion = ops.concat_tokens_bwd(dx.contiguous().float(), T_rgb, T_motion, len_rgb, len_motion)
+        return drgb, dmotion, None, None, None, None, None
+
+
+def concat_tokens(rgb, motion, mask_rgb, mask_motion, T_out, len_rgb=None, len_motion=None):
+    return ConcatTokensFn.apply(rgb, motion, mask_rgb, mask_motion, T_out, len_rgb, len_motion)

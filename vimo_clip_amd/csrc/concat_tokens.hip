@@ -105,3 +105,71 @@ extern "C" int vmc_concat_tokens_len(const float* rgb, const float* motion, cons
   VMC_CHECK_LAUNCH();
   return 0;
 }
+
+// ---- backward: the scatter of dx [B, T_out, D] back to the two streams ------------------------------------------------------------------
+//   d rgb[b, t]    = dx[b, t]         for t < keep,  0 on rows keep..T_rgb-1 (the dropped last RGB row and the padding)
+//   d motion[b, t] = dx[b, keep + t]  for t < nm,    0 on rows nm..T_motion-1
+// with keep / nm clamped exactly as in the forward, from the same device values.  Every output row has ONE source row (or none), so
+// it is one pass of plain vector stores: no atomics, and every element of both gradients is written on every call.
+//   grid = (ceil(max(T_rgb, T_motion) / CT_ROWS), B, 2): z = 0 writes d rgb, z = 1 d motion; a workgroup owns CT_ROWS rows of one clip.
+// BOUNDS: a destination row is < T_rgb (z = 0) or < T_motion (z = 1); a source row is < keep <= T_out or keep + t < keep + nm <= T_out.
+struct CtBwdArgs {
+  const float* dx;
+  float* drgb;
+  float* dmotion;
+  const int* len_rgb;
+  const int* len_motion;
+  int B, T_rgb, T_motion, T_out, D;
+  int vec;        // 16-byte path: D % 4 == 0, dx, drgb and dmotion 16-byte aligned
+};
+
+__global__ void __launch_bounds__(256) concat_tokens_len_bwd_kernel(const CtBwdArgs a) {
+  const int b = blockIdx.y, T_out = a.T_out, D = a.D;
+  int nr = a.len_rgb != nullptr ? *a.len_rgb : a.T_rgb;
+  int nm = a.len_motion != nullptr ? *a.len_motion : a.T_motion;
+  nr = nr < 1 ? 1 : (nr > a.T_rgb ? a.T_rgb : nr);
+  nm = nm < 1 ? 1 : (nm > a.T_motion ? a.T_motion : nm);
+  const int keep = nr - 1 < T_out ? nr - 1 : T_out;
+  nm = nm < T_out - keep ? nm : T_out - keep;
+
+  const bool mot = blockIdx.z == 1;
+  const int T_dst = mot ? a.T_motion : a.T_rgb, n_src = mot ? nm : keep, s0 = mot ? keep : 0;
+  float* dst_base = mot ? a.dmotion : a.drgb;
+  const int t0 = blockIdx.x * CT_ROWS;
+  const int t1 = t0 + CT_ROWS < T_dst ? t0 + CT_ROWS : T_dst;
+  for (int t = t0; t < t1; ++t) {
+    const float* src = t < n_src ? a.dx + ((size_t)b * T_out + s0 + t) * D : nullptr;      // nullptr: a zero row
+    float* dst = dst_base + ((size_t)b * T_dst + t) * D;
+    if (a.vec) {
+      const int D4 = D >> 2;
+      const float4* s4 = (const float4*)src;
+      float4* d4 = (float4*)dst;
+      for (int e = threadIdx.x; e < D4; e += 256) d4[e] = src != nullptr ? s4[e] : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      for (int e = threadIdx.x; e < D; e += 256) dst[e] = src != nullptr ? src[e] : 0.f;
+    }
+  }
+}
+
+extern "C" int vmc_concat_tokens_len_bwd(const float* dx, float* drgb, float* dmotion, int B, int T_rgb, int T_motion, int T_out, int D,
+                                         const int* len_rgb, const int* len_motion, void* stream) {
+  if (!dx || !drgb || !dmotion) return VMC_E_ARG;
+  if (B <= 0 || T_rgb <= 0 || T_motion <= 0 || T_out <= 0 || D <= 0 || B > 65535) return VMC_E_SHAPE;
+  CtBwdArgs a = {};
+  a.dx = dx;
+  a.drgb = drgb;
+  a.dmotion = dmotion;
+  a.len_rgb = len_rgb;
+  a.len_motion = len_motion;
+  a.B = B;
+  a.T_rgb = T_rgb;
+  a.T_motion = T_motion;
+  a.T_out = T_out;
+  a.D = D;
+  a.vec = D % 4 == 0 && (((uintptr_t)dx | (uintptr_t)drgb | (uintptr_t)dmotion) & 15) == 0;
+  const int T_max = T_rgb > T_motion ? T_rgb : T_motion;
+  const dim3 grid((unsigned)((T_max + CT_ROWS - 1) / CT_ROWS), (unsigned)B, 2);
+  hipLaunchKernelGGL(concat_tokens_len_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+  VMC_CHECK_LAUNCH();
+  return 0;
+}

@@ -26,7 +26,7 @@ struct TfArgs {
   const uint16_t* W;        // [N, K] 16-bit, row stride ldw
   int ldw;
   const float* bias;
-  const float* resid;       // EPI_RESID32: fp32 [M, ldres]
+  const float* resid;       // EPI_RESID32: fp32 [M, ldres] (training ring: NULL = no residual operand)
   int ldres;
   void* out;
   int ldo;
@@ -851,7 +851,8 @@ __global__ void __launch_bounds__(TF_NTH) tf_gemm_ring_kernel(const TfArgs a) {
         const f32x4 o = *(const f32x4*)(red + ((rt * NTN + n) * 64 + lane) * 16);
         if constexpr (TR) {
           const int col = n0 + 16 * n + 4 * q;
-          const float4 rr = col < a.N ? *(const float4*)(a.resid + (size_t)grow * a.ldres + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+          // no residual operand: the first term of a sum that later launches extend through theirs (dMotion, tfam_route.h)
+          const float4 rr = (col < a.N && a.resid != nullptr) ? *(const float4*)(a.resid + (size_t)grow * a.ldres + col) : make_float4(0.f, 0.f, 0.f, 0.f);
           tf_epilogue_train<T, EPI_RESID32>(a, grow, col, acc[n] + o, false, nullptr, rr);
         } else {
           tf_epilogue<T, EPI_RESID32>(a, grow, n0 + 16 * n + 4 * q, acc[n] + o);

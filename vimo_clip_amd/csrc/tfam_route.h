@@ -727,3 +727,76 @@ static inline TrProjWs tr_proj_ws(void* base, const TfDims& d) {
 static inline size_t tfam_train_proj_workspace_bytes(const TfDims& d) { return tr_proj_ws(nullptr, d).bytes; }
 // offset of dx0 (rows behind the pool length are exactly zero there)
 static inline long long tfam_train_proj_dx0_offset(const TfDims& d) { return (long long)(uintptr_t)tr_proj_ws(nullptr, d).dx0; }
+
+// ---- gradients wrt the input tokens (training chains; opt-in: AMO_CLIP.fused_input_grads) -----------------------------------------
+// What the backward adds when the caller's token tensors require a gradient.  Nothing above changes: the launches below follow the
+// existing ones and write into a workspace extension behind tr_ws (without a projection) or behind tr_proj_ws (with one).
+//   dX       [M, D]   fp32  L8 of layer 0, dX = dy1 + dqkv Wqkv: the K = 3 D ring every other layer runs.  Rows at and behind the pool
+//                           length are exact zeros (masked as keys, not pooled: no gradient reaches them).
+//   dMotion  [Mk, D]  fp32  cross attention: sum over the layers of dkv16_l Wkv_l, K = 2 D ring over a column window of wt_cross_in
+//                           (leading dimension 3 D), one launch behind each layer's cross-attention backward.  Layer L - 1 writes, the
+//                           layers below add through the launch's residual operand: fp32, one fixed order, bit for bit repeatable.
+//   dXcat    [M, 2 D] fp32  projection mode: d0_16 Wp, one single-shot launch behind layer 0's L8 (N = 2 D, K = D, no bias, no residual).
+// The single-shot kernel is compiled already (tf_run_single<PRO_16, EPI_BIAS32> builds the whole BN x KD product for the classifier), but
+// no shape of kTfamInsts reaches it at K = d_model; it is listed here.
+constexpr TfamInst kTfamInputInsts[] = {
+    {TFAM_SINGLE, 16, PRO_16, EPI_BIAS32, 512, 64, 1, 1, 1, 0, 0, 64 * TF_NW},
+    {TFAM_SINGLE, 16, PRO_16, EPI_BIAS32, 768, 64, 1, 1, 1, 0, 0, 64 * TF_NW},
+    {TFAM_RING, TF_RING_BN, 0, 0, 0, 0, 0, 0, 1, TF_RING_KC, 0, TF_NTH},
+    {TFAM_RING, TF_RING_BN, 0, 0, 0, 0, 0, 0, 1, TR_RING_KC_ALT, 0, TF_NTH},
+};
+constexpr int kTfamInputInstCount = sizeof(kTfamInputInsts) / sizeof(kTfamInputInsts[0]);
+static inline int tfam_find_input_inst(const TfamPlan& p) {
+  for (int i = 0; i < kTfamInputInstCount; ++i) {
+    const TfamInst& k = kTfamInputInsts[i];
+    if (k.family == p.family && k.bn == p.bn && k.pro == p.pro && k.epi == p.epi && k.kd == p.kd && k.dh == p.dh && k.qt == p.qt &&
+        k.nkt == p.nkt && k.tr == p.tr && k.kc == p.kc && k.maxb == p.maxb)
+      return i;
+  }
+  return -1;
+}
+
+// dX: L8 of layer 0, the plan of the other layers' L8
+static inline TfamPlan tfam_route_input_dx(const TfDims& d, const TfamBlocks& b) { return tfam_plan_ring(b.M, d.D, 3 * d.D, b.rpb, true); }
+// dMotion of one layer: the motion rows in uniform 32-row blocks (as the forward's K|V projection); K = 2 D is 1024 or 1536: KC = 512
+static inline TfamPlan tfam_route_input_dmotion(const TfDims& d, const TfamBlocks& b) {
+  if (!d.has_cross) return TfamPlan();
+  return tfam_plan_ring(b.Mk, d.D, 2 * d.D, TF_BM, true);
+}
+// dXcat.  The 16-column tile: (32 + 16) x 768 x 2 B of LDS lets two workgroups share a CU, and 2 D / 16 x M / 32 <= 768 workgroups
+// keep every CU streaming its own rows of Wp^T.
+static inline TfamPlan tfam_route_input_dxcat(const TfDims& d) {
+  return tfam_plan_single(16, PRO_16, EPI_BIAS32, d.B * d.T, 2 * d.D, d.D, TF_BM, true);
+}
+// The supported set: that of the chain itself (tfam_check(train), or tfam_check_proj with d.proj), and 15 the launches above plan.
+static inline int tfam_check_input(const TfDims& d) {
+  if (int rc = d.proj ? tfam_check_proj(d) : tfam_check(d, true)) return rc;
+  const TfamBlocks b = tfam_blocks(d);
+  if (d.proj) return tfam_route_input_dxcat(d).rc;
+  if (int rc = tfam_route_input_dx(d, b).rc) return rc;
+  return tfam_route_input_dmotion(d, b).rc;
+}
+
+// Workspace extension, laid out BEHIND the training workspace (d.proj: behind the projection's extension).
+struct TrInputWs {
+  float* dx;                // [M, D]    no projection: gradient wrt the pooled stream's tokens
+  float* dmotion;           // [Mk, D]   cross attention: gradient wrt the motion tokens
+  float* dxcat;             // [M, 2D]   projection: gradient wrt the concatenated features
+  size_t bytes;             // of the whole workspace, tr_ws (and tr_proj_ws) included
+};
+static inline TrInputWs tr_input_ws(void* base, const TfDims& d) {
+  const size_t M = (size_t)d.B * d.T, Mk = (size_t)d.B * (d.has_cross ? d.Tk : 0), D = d.D;
+  char* p = (char*)base;
+  TrInputWs w = {};
+  size_t o = d.proj ? tr_proj_ws(nullptr, d).bytes : tr_ws(nullptr, d).bytes;
+  auto take = [&](size_t n) { char* q = p + o; o += tr_al(n); return q; };
+  if (d.proj) {
+    w.dxcat = (float*)take(M * 2 * D * 4);
+  } else {
+    w.dx = (float*)take(M * D * 4);
+    if (d.has_cross) w.dmotion = (float*)take(Mk * D * 4);
+  }
+  w.bytes = o;
+  return w;
+}
+static inline size_t tfam_train_input_workspace_bytes(const TfDims& d) { return tr_input_ws(nullptr, d).bytes; }

@@ -21,6 +21,9 @@
 // Feature-concatenation mode (the _proj entries; tfam_route.h, last section): F0 x32 = 16bit(xcat) Wp^T + bp in front of layer 0, whose
 // F1 / F2 read x32 as their tokens; L8 runs for layer 0 too (dx0 and its 16-bit copy into the workspace extension), and the projection's
 // weight / bias gradient d0_16^T xcat16 is one more problem of the grouped launch that holds layer 0's.
+// Gradients wrt the input tokens (the _inputs entries; tfam_route.h, last section): L8 runs for layer 0 into the input extension (dX),
+// every layer's cross-attention backward is followed by dMotion (+)= dkv Wkv (K = 2D ring), and the projection mode adds
+// dXcat = d0_16 Wp behind layer 0's L8.
 // and ONE grouped launch (tr_wgrad_group_kernel) for the seven weight gradients dW = dY^T X (contraction over the <= 256
 // token rows: the TN body of gemm_tn.hip, one 256 x 128 tile per workgroup), their bias gradients (ones-MFMA on the dY
 // fragments) and the three LayerNorms' gamma / beta gradients.
@@ -475,7 +478,7 @@ int tr_wgrad_launch(const TrWgradGroup& g, hipStream_t s) {
 template <typename T>
 int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, const TfDims& d, const TrWs& ws,
                  float p, const uint64_t* seeds, int dtype16, hipStream_t s, TrWgradGroup* defer = nullptr, const TrProjWs* pw = nullptr,
-                 const vmc_tfam_proj_params* pp = nullptr) {
+                 const vmc_tfam_proj_params* pp = nullptr, const TrInputWs* iw = nullptr, int want = 0, const void* wt_proj = nullptr) {
   const TfamBlocks bk = tfam_blocks(d);
   const TfamStep<TFAM_B_COUNT> plan = tfam_route_layer_bwd(d, bk, layer == 0, tr_overrides());
   if (plan.rc) return plan.rc;
@@ -520,6 +523,14 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
     if ((rc = vmc_attention_bwd(w.q16, w.kv16, w.kv16 + D, mask_kv, w.o_cross, w.doc16, w.lse_cross, w.dq16, w.dkv16, w.dkv16 + D, d.B, d.H, d.T,
                                 d.Tk, dh, D, 2 * D, 2 * D, D, D, 2 * D, 2 * D, drop ? p : 0.f, drop ? seeds[2] : 0, w.attn_ws, aws, dtype16, s)))
       return rc;
+    if (iw != nullptr && (want & VMC_TFAM_WANT_DMOTION)) {  // dMotion = [dMotion of the layers above +] dkv Wkv
+      TfArgs a = {};
+      a.M = Mk; a.N = D; a.K = 2 * D; a.rpb = TF_BM;
+      a.A = w.dkv16; a.lda = 2 * D;
+      a.W = (const uint16_t*)P.wt_cross_in + D; a.ldw = 3 * D;      // columns D:3D of the transposed packed in_proj = Wkv^T
+      a.resid = layer == d.L - 1 ? nullptr : iw->dmotion; a.ldres = D; a.out = iw->dmotion; a.ldo = D;
+      if ((rc = tf_run_ring<T, true>(a, tfam_route_input_dmotion(d, bk), s))) return rc;
+    }
     {  // L5: dx1 = dy2 + dq Wq
       TfArgs a = {};
       a.M = M; a.N = D; a.K = D; a.rpb = rpb;
@@ -546,15 +557,25 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
                               dtype16, s)))
     return rc;
   const bool proj = layer == 0 && pw != nullptr;      // feature mode: layer 0's input is the projection's output, which needs its gradient
-  if (layer > 0 || proj) {  // L8: dx3 of the layer below (dx0 of the projection) = dy1 + dqkv Wqkv
+  const bool dx_in = layer == 0 && !proj && iw != nullptr && (want & VMC_TFAM_WANT_DX);      // the caller's tokens want their gradient
+  if (layer > 0 || proj || dx_in) {  // L8: dx3 of the layer below (dx0 of the projection, dX of the tokens) = dy1 + dqkv Wqkv
     TfArgs a = {};
     a.M = M; a.N = D; a.K = 3 * D; a.rpb = rpb;
     a.A = w.dqkv16; a.lda = 3 * D;
     a.W = (const uint16_t*)P.wt_self_in; a.ldw = 3 * D;
     a.resid = w.dy1; a.ldres = D; a.ldo = D;
     if (proj) { a.out = pw->dx0; a.y16out = pw->d0_16; }
+    else if (dx_in) a.out = iw->dx;
     else a.out = tr_lw(ws, d, layer - 1).dx3;
-    if ((rc = tf_run_ring<T, true>(a, proj ? tfam_route_proj_bwd(d, bk) : plan.p[TFAM_B_DX0], s))) return rc;
+    if ((rc = tf_run_ring<T, true>(a, proj ? tfam_route_proj_bwd(d, bk) : dx_in ? tfam_route_input_dx(d, bk) : plan.p[TFAM_B_DX0], s))) return rc;
+  }
+  if (proj && iw != nullptr && (want & VMC_TFAM_WANT_DX)) {  // dXcat = d0_16 Wp
+    TfArgs a = {};
+    a.M = M; a.N = 2 * D; a.K = D; a.rpb = TF_BM;
+    a.A = pw->d0_16; a.lda = D;
+    a.W = (const uint16_t*)wt_proj; a.ldw = D;
+    a.out = iw->dxcat; a.ldo = 2 * D;
+    if ((rc = tf_run_single<T, PRO_16, EPI_BIAS32, true>(a, tfam_route_input_dxcat(d), s))) return rc;
   }
   // weight, bias and LayerNorm-parameter gradients: one grouped launch
   TrWgradGroup local = {};
@@ -578,6 +599,27 @@ int tr_layer_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_lay
 }
 
 inline bool tr_ws_ok(const void* ws, size_t bytes, const TrWs& w) { return ws != nullptr && bytes >= w.bytes && (((uintptr_t)ws) & 255) == 0; }
+
+// The whole backward behind the head: the dgrad chains of all layers, then every weight gradient in ONE launch (the per-layer entry
+// points launch their own).  TR_WGRAD_FLUSH layers' problems fit the table; deeper models flush it that often (tfam_wgrad_flush); with
+// a projection the last launch holds layer 0's problems and the projection's.
+int tr_layers_bwd(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, const TfDims& d, const TrWs& ws, float p_drop,
+                  const uint64_t* seeds, int dtype16, hipStream_t s, const TrProjWs* pw = nullptr, const vmc_tfam_proj_params* pp = nullptr,
+                  const TrInputWs* iw = nullptr, int want = 0, const void* wt_proj = nullptr) {
+  TrWgradGroup g = {};
+  for (int l = d.L - 1; l >= 0; --l) {
+    const uint64_t* sl = seeds ? seeds + 7 * l : nullptr;
+    int rc = dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, mask_kv, layers, l, d, ws, p_drop, sl, dtype16, s, &g, pw, pp, iw, want, wt_proj)
+                                 : tr_layer_bwd<F16>(mask, mask_kv, layers, l, d, ws, p_drop, sl, dtype16, s, &g, pw, pp, iw, want, wt_proj);
+    if (rc) return rc;
+    if (tfam_wgrad_flush(d.L, l)) {
+      rc = dtype16 == VMC_BF16 ? tr_wgrad_launch<BF16>(g, s) : tr_wgrad_launch<F16>(g, s);
+      if (rc) return rc;
+      g = TrWgradGroup{};
+    }
+  }
+  return 0;
+}
 
 }  // namespace
 
@@ -683,20 +725,7 @@ extern "C" int vmc_tfam_train_bwd_len(const float* dlogits, const uint8_t* mask,
   if (rc) return rc;
   TR_PROLOG();
   if (!layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
-  // the dgrad chains of all layers first, then every weight gradient in ONE launch (the per-layer entry point launches its own).
-  // TR_WGRAD_FLUSH layers' problems fit the table; deeper models flush it that often (tfam_wgrad_flush).
-  TrWgradGroup g = {};
-  for (int l = L - 1; l >= 0; --l) {
-    rc = dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, mask_kv, layers, l, d, ws, p_drop, seeds ? seeds + 7 * l : nullptr, dtype16, s, &g)
-                             : tr_layer_bwd<F16>(mask, mask_kv, layers, l, d, ws, p_drop, seeds ? seeds + 7 * l : nullptr, dtype16, s, &g);
-    if (rc) return rc;
-    if (tfam_wgrad_flush(L, l)) {
-      rc = dtype16 == VMC_BF16 ? tr_wgrad_launch<BF16>(g, s) : tr_wgrad_launch<F16>(g, s);
-      if (rc) return rc;
-      g = TrWgradGroup{};
-    }
-  }
-  return 0;
+  return tr_layers_bwd(mask, mask_kv, layers, d, ws, p_drop, seeds, dtype16, s);
 }
 extern "C" int vmc_tfam_train_bwd(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
                                   const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff,
@@ -778,19 +807,93 @@ extern "C" int vmc_tfam_train_bwd_proj(const float* dlogits, const vmc_tfam_proj
   int rc = vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, 0, D, H, ff, L, C, 0, p_mlp, seeds ? seeds[7 * L] : 0, pool_len,
                                  dtype16, stream);
   if (rc) return rc;
-  // as vmc_tfam_train_bwd_len: every dgrad chain, then the weight gradients in one launch per tfam_wgrad_flush; the last one holds
-  // layer 0's problems and the projection's
-  TrWgradGroup g = {};
-  for (int l = L - 1; l >= 0; --l) {
-    const uint64_t* sl = seeds ? seeds + 7 * l : nullptr;
-    rc = dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, nullptr, layers, l, d, ws, p_drop, sl, dtype16, s, &g, &pw, proj)
-                             : tr_layer_bwd<F16>(mask, nullptr, layers, l, d, ws, p_drop, sl, dtype16, s, &g, &pw, proj);
-    if (rc) return rc;
-    if (tfam_wgrad_flush(L, l)) {
-      rc = dtype16 == VMC_BF16 ? tr_wgrad_launch<BF16>(g, s) : tr_wgrad_launch<F16>(g, s);
-      if (rc) return rc;
-      g = TrWgradGroup{};
-    }
+  return tr_layers_bwd(mask, nullptr, layers, d, ws, p_drop, seeds, dtype16, s, &pw, proj);
+}
+
+// ---- gradients wrt the input tokens: the backward entries that also fill the input extension ------------------------------------------
+#define TR_INPUT_DIMS() TfDims d = {B, T, has_cross ? Tk : 0, D, H, ff, L, C, has_cross ? 1 : 0, proj ? 1 : 0}
+
+extern "C" int vmc_tfam_input_grad_supported(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj) {
+  TR_INPUT_DIMS();
+  return tfam_check_input(d);
+}
+extern "C" size_t vmc_tfam_train_input_workspace_bytes(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj) {
+  TR_INPUT_DIMS();
+  if (tfam_check_input(d)) return 0;
+  return tfam_train_input_workspace_bytes(d);
+}
+extern "C" int vmc_tfam_train_input_grad_offsets(int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross, int proj,
+                                                 long long* offsets) {
+  TR_INPUT_DIMS();
+  if (!offsets) return VMC_E_ARG;
+  offsets[0] = offsets[1] = offsets[2] = -1;
+  if (int rc = tfam_check_input(d)) return rc;
+  const TrInputWs iw = tr_input_ws(nullptr, d);
+  if (d.proj) {
+    offsets[2] = (long long)(uintptr_t)iw.dxcat;
+  } else {
+    offsets[0] = (long long)(uintptr_t)iw.dx;
+    if (d.has_cross) offsets[1] = (long long)(uintptr_t)iw.dmotion;
   }
   return 0;
+}
+
+#define TR_INPUT_PROLOG(PROJ)                                                                                 \
+  TfDims d = {B, T, Tk, D, H, ff, L, C, has_cross, PROJ};                                                     \
+  if (int rc_ = tfam_check_input(d)) return rc_;                                                              \
+  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;                                          \
+  if (want & ~(VMC_TFAM_WANT_DX | VMC_TFAM_WANT_DMOTION)) return VMC_E_ARG;                                   \
+  if ((want & VMC_TFAM_WANT_DMOTION) && !has_cross) return VMC_E_ARG;                                         \
+  const TrWs ws = tr_ws(workspace, d);                                                                        \
+  const TrInputWs iw = tr_input_ws(workspace, d);                                                             \
+  if (workspace == nullptr || workspace_bytes < iw.bytes || (((uintptr_t)workspace) & 255)) return VMC_E_ARG; \
+  hipStream_t s = (hipStream_t)stream
+
+extern "C" int vmc_tfam_layer_bwd_inputs(const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers, int layer, void* workspace,
+                                         size_t workspace_bytes, int B, int T, int Tk, int D, int H, int ff, int L, int C, int has_cross,
+                                         float p_drop, const uint64_t* seeds, int want, int dtype16, void* stream) {
+  TR_INPUT_PROLOG(0);
+  if (!layers || layer < 0 || layer >= L || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
+  return dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, mask_kv, layers, layer, d, ws, p_drop, seeds, dtype16, s, nullptr, nullptr, nullptr, &iw, want)
+                             : tr_layer_bwd<F16>(mask, mask_kv, layers, layer, d, ws, p_drop, seeds, dtype16, s, nullptr, nullptr, nullptr, &iw, want);
+}
+
+extern "C" int vmc_tfam_train_bwd_inputs_len(const float* dlogits, const uint8_t* mask, const uint8_t* mask_kv, const vmc_tfam_layer_params* layers,
+                                             const vmc_tfam_head_params* head, void* workspace, size_t workspace_bytes, int B, int T, int Tk, int D,
+                                             int H, int ff, int L, int C, int has_cross, float p_drop, float p_mlp, const uint64_t* seeds,
+                                             const int* pool_len, int want, int dtype16, void* stream) {
+  if (p_mlp > 0.f && !seeds) return VMC_E_ARG;
+  TR_INPUT_PROLOG(0);
+  if (!layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG;
+  int rc = vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, Tk, D, H, ff, L, C, has_cross, p_mlp,
+                                 seeds ? seeds[7 * L] : 0, pool_len, dtype16, stream);
+  if (rc) return rc;
+  return tr_layers_bwd(mask, mask_kv, layers, d, ws, p_drop, seeds, dtype16, s, nullptr, nullptr, &iw, want);      // the input launches sit inside the layers' dgrad chains
+}
+
+#define TR_INPUT_PROJ_PROLOG()                  \
+  const int Tk = 0, has_cross = 0;              \
+  const int want = VMC_TFAM_WANT_DX;            \
+  TR_INPUT_PROLOG(1);                           \
+  const TrProjWs pw = tr_proj_ws(workspace, d); \
+  if (!proj || !wt_proj || !layers || (p_drop > 0.f && !seeds)) return VMC_E_ARG
+
+extern "C" int vmc_tfam_layer0_bwd_proj_inputs(const vmc_tfam_proj_params* proj, const void* wt_proj, const uint8_t* mask,
+                                               const vmc_tfam_layer_params* layers, void* workspace, size_t workspace_bytes, int B, int T, int D, int H,
+                                               int ff, int L, int C, float p_drop, const uint64_t* seeds, int dtype16, void* stream) {
+  TR_INPUT_PROJ_PROLOG();
+  return dtype16 == VMC_BF16 ? tr_layer_bwd<BF16>(mask, nullptr, layers, 0, d, ws, p_drop, seeds, dtype16, s, nullptr, &pw, proj, &iw, want, wt_proj)
+                             : tr_layer_bwd<F16>(mask, nullptr, layers, 0, d, ws, p_drop, seeds, dtype16, s, nullptr, &pw, proj, &iw, want, wt_proj);
+}
+
+extern "C" int vmc_tfam_train_bwd_inputs_proj(const float* dlogits, const vmc_tfam_proj_params* proj, const void* wt_proj, const uint8_t* mask,
+                                              const vmc_tfam_layer_params* layers, const vmc_tfam_head_params* head, void* workspace,
+                                              size_t workspace_bytes, int B, int T, int D, int H, int ff, int L, int C, float p_drop, float p_mlp,
+                                              const uint64_t* seeds, const int* pool_len, int dtype16, void* stream) {
+  if (p_mlp > 0.f && !seeds) return VMC_E_ARG;
+  TR_INPUT_PROJ_PROLOG();
+  int rc = vmc_tfam_head_bwd_len(dlogits, layers, head, workspace, workspace_bytes, B, T, 0, D, H, ff, L, C, 0, p_mlp, seeds ? seeds[7 * L] : 0, pool_len,
+                                 dtype16, stream);
+  if (rc) return rc;
+  return tr_layers_bwd(mask, nullptr, layers, d, ws, p_drop, seeds, dtype16, s, &pw, proj, &iw, want, wt_proj);
 }

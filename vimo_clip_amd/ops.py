@@ -419,6 +419,19 @@ def pool_len_tensor(pool_len, device):
     return torch.tensor([int(pool_len)], dtype=torch.int32, device=device)
 
 
+def concat_tokens_bwd(dx: torch.Tensor, T_rgb: int, T_motion: int, len_rgb=None, len_motion=None):
+    """(d rgb [B, T_rgb, D], d motion [B, T_motion, D]) = vmc_concat_tokens_len_bwd: the rows of ``dx`` [B, T_out, D] f32 scattered back to
+    the two streams at the lengths ``concat_tokens`` read; exact zeros on every row that fed nothing.  Only enqueues."""
+    if dx.dtype != torch.float32 or not dx.is_contiguous() or dx.dim() != 3:
+        raise ValueError("concat_tokens_bwd: need a contiguous float32 [B, T_out, D] gradient")
+    B, T_out, D = dx.shape
+    drgb = torch.empty((B, int(T_rgb), D), dtype=torch.float32, device=dx.device)
+    dmotion = torch.empty((B, int(T_motion), D), dtype=torch.float32, device=dx.device)
+    check(lib.vmc_concat_tokens_len_bwd(ptr(dx), ptr(drgb), ptr(dmotion), B, int(T_rgb), int(T_motion), T_out, D, ptr(len_rgb),
+                                        ptr(len_motion), stream()), "concat_tokens_len_bwd")
+    return drgb, dmotion
+
+
 def mean_pool(x: torch.Tensor, B: int, T: int, D: int, dtype16, out16=True, out32=False, pool_len=None):
     """pool_len (one-element int32 device tensor or None): the mean runs over the first pool_len rows of every clip."""
     o16 = torch.empty((B, D), dtype=dtype16, device=x.device) if out16 else None

@@ -12,6 +12,10 @@ the per-op path (AttentionLayer.run), so both paths apply identical masks.
 The feature concatenation (use_cross_attention=False, concat_dim=-1; AMO_CLIP.fused_feature_training) takes the ``_proj`` entries:
 the chain starts at projection_layer, one launch in front of layer 0, and the projection's gradients come out of the grouped
 weight-gradient launch that holds layer 0's (``forward_train(..., proj=True)`` with the concatenated features as ``x``).
+
+Gradients wrt the tokens (AMO_CLIP.fused_input_grads): when ``x`` / ``motion`` require grad, the workspace grows by an extension, the
+backward takes the ``_inputs`` entries (one more launch for ``x``, one per layer for ``motion``, one for the feature concatenation) and
+the node returns the gradients as views of that extension.  Off, or with tokens that do not require grad, nothing changes.
 """
 from __future__ import annotations
 
@@ -49,6 +53,7 @@ class ProjParams(ctypes.Structure):           # vmc_tfam_proj_params
 
 
 SEEDS_PER_LAYER = 7
+WANT_DX, WANT_DMOTION = 1, 2                 # VMC_TFAM_WANT_*
 
 
 def supported(model, B, T, Tk, has_cross) -> bool:
@@ -73,6 +78,21 @@ def supported_proj(model, B, T) -> bool:
 _proj_answers = {}
 
 
+def supported_inputs(model, B, T, Tk, has_cross, proj=False) -> bool:
+    """Batches whose training chains also return the gradients wrt the tokens: ``supported`` / ``supported_proj`` over the shapes
+    vmc_tfam_input_grad_supported accepts."""
+    if not (supported_proj(model, B, T) if proj else supported(model, B, T, Tk, has_cross)):
+        return False
+    key = tfam_fused.dims(model, B, T, Tk, has_cross) + (int(bool(proj)),)
+    ok = _input_answers.get(key)
+    if ok is None:
+        ok = _input_answers[key] = lib.vmc_tfam_input_grad_supported(*key) == 0
+    return ok
+
+
+_input_answers = {}
+
+
 def _grad_dst(p, fresh):
     """Gradient destination of a parameter: its arena slot, or a new fp32 tensor handed back to autograd."""
     if p is None or not p.requires_grad:
@@ -89,8 +109,10 @@ def _grad_dst(p, fresh):
 class _Tables:
     """ctypes arrays of vmc_tfam_layer_params / vmc_tfam_head_params for one (model, compute dtype)."""
 
-    def __init__(self, model, dtype16, cross, proj=False):
+    def __init__(self, model, dtype16, cross, proj=False, inputs=False):
         self.model, self.dtype16, self.cross, self.proj = model, dtype16, cross, proj
+        self.inputs = inputs      # with proj: also the transposed projection weight (the dgrad wrt the concatenated features reads it)
+        self.wt_proj = None
         self.key = None
         self.keep = []
 
@@ -188,6 +210,9 @@ class _Tables:
             keep.append(ag.weights.get(pl.weight, d16))
             pp.w_proj, pp.b_proj = keep[-1].data_ptr(), f(pl.bias)
             pp.gw_proj, pp.gb_proj = g(pl.weight), g(pl.bias)
+            if self.inputs:
+                self.wt_proj = ag.weights.get(pl.weight, d16, transposed=True)      # its own buffer: the plain copy other tables point at stays
+                keep.append(self.wt_proj)
         if fresh is None:
             self.key, self.layers, self.head, self.projp, self.keep = key, layers, h, pp, keep
         else:
@@ -195,18 +220,21 @@ class _Tables:
         return layers, h, pp
 
 
-def _tables(model, dtype16, cross, proj=False) -> _Tables:
+def _tables(model, dtype16, cross, proj=False, inputs=False) -> _Tables:
     tabs = model.__dict__.setdefault("_tfam_train_tables", {})
-    t = tabs.get((dtype16, cross, proj))
+    key = (dtype16, cross, proj, True) if inputs else (dtype16, cross, proj)
+    t = tabs.get(key)
     if t is None:
-        t = tabs[(dtype16, cross, proj)] = _Tables(model, dtype16, cross, proj)
+        t = tabs[key] = _Tables(model, dtype16, cross, proj, inputs)
     return t
 
 
 class TfamTrainFn(torch.autograd.Function):
     """logits = AMO_CLIP(x, motion) in train mode.  Inputs after ``proj`` are the parameters (so that autograd asks for their
     gradients); their values are read through the pointer tables, not through these tensors.  ``proj``: x is the feature
-    concatenation [B, T, 2 D] and the chain starts at projection_layer (the vmc_tfam_*_proj entries)."""
+    concatenation [B, T, 2 D] and the chain starts at projection_layer (the vmc_tfam_*_proj entries).  When ``x`` / ``motion``
+    require grad (forward_train lets that through with AMO_CLIP.fused_input_grads only) the backward takes the ``_inputs`` entries
+    and returns their gradients: views of the workspace extension, taken before the workspace is released."""
 
     @staticmethod
     def forward(ctx, model, x, motion, mask, mask_kv, cross, p_drop, p_mlp, seeds, pool_len, proj, *params):
@@ -214,10 +242,14 @@ class TfamTrainFn(torch.autograd.Function):
         B, T, _ = x.shape
         Tk = motion.shape[1] if cross else 0
         dims = tfam_fused.dims(model, B, T, Tk, cross)
-        tab = _tables(model, dt16, cross, proj)
+        want = (WANT_DX if ctx.needs_input_grad[1] else 0) | (WANT_DMOTION if cross and ctx.needs_input_grad[2] else 0)
+        tab = _tables(model, dt16, cross, proj, inputs=bool(want) and proj)
         layers, head, projp = tab.build()
         pdims = dims[:2] + dims[3:8]                         # the _proj entries take neither Tk nor has_cross
-        nbytes = lib.vmc_tfam_train_proj_workspace_bytes(*pdims) if proj else lib.vmc_tfam_train_workspace_bytes(*dims)
+        if want:                                             # the same workspace with the input extension behind it
+            nbytes = lib.vmc_tfam_train_input_workspace_bytes(*dims, int(proj))
+        else:
+            nbytes = lib.vmc_tfam_train_proj_workspace_bytes(*pdims) if proj else lib.vmc_tfam_train_workspace_bytes(*dims)
         if nbytes == 0:
             raise RuntimeError("vmc_tfam_train_workspace_bytes: unsupported shape")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -233,6 +265,7 @@ class TfamTrainFn(torch.autograd.Function):
         ctx.model, ctx.tab, ctx.ws, ctx.dims, ctx.cross, ctx.proj = model, tab, ws, dims, cross, proj
         ctx.masks, ctx.drop, ctx.sarr, ctx.params = (mask, mask_kv), (float(p_drop), float(p_mlp)), sarr, params
         ctx.pool_len = pool_len                              # the backward reads the same device value
+        ctx.want = want
         return logits
 
     @staticmethod
@@ -257,10 +290,20 @@ class TfamTrainFn(torch.autograd.Function):
         done = getattr(model, "grad_group_callback", None)      # e.g. FusedAdam.group_ready: the optimiser step of a finished group
         c = model.classifier
         head_params = (c[4].weight, c[4].bias, c[1].weight, c[1].bias, c[0].weight, c[0].bias)
+        want = ctx.want
+        wt_proj = ptr(tab.wt_proj) if (want and proj) else None
         if not ag.grad_ready_hooks and done is None:
             # nobody waits for a layer's gradients (single process): the whole backward in one call -- the dgrad chains of all layers,
             # then every weight gradient in ONE grouped launch (vmc_tfam_train_bwd)
-            if proj:
+            if want and proj:
+                check(lib.vmc_tfam_train_bwd_inputs_proj(ptr(dlogits), ctypes.byref(projp), wt_proj, ptr(mask), layers, ctypes.byref(head),
+                                                         ptr(ws), nbytes, *pdims, p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()),
+                      "tfam_train_bwd_inputs_proj")
+            elif want:
+                check(lib.vmc_tfam_train_bwd_inputs_len(ptr(dlogits), ptr(mask), ptr(mask_kv) if cross else None, layers, ctypes.byref(head),
+                                                        ptr(ws), nbytes, *dims, p_drop, p_mlp, sarr, ptr(pool_len), want, dt(dt16), stream()),
+                      "tfam_train_bwd_inputs")
+            elif proj:
                 check(lib.vmc_tfam_train_bwd_proj(ptr(dlogits), ctypes.byref(projp), ptr(mask), layers, ctypes.byref(head), ptr(ws), nbytes, *pdims,
                                                   p_drop, p_mlp, sarr, ptr(pool_len), dt(dt16), stream()), "tfam_train_bwd_proj")
             else:
@@ -274,7 +317,13 @@ class TfamTrainFn(torch.autograd.Function):
             if done is not None:                                 # group L = the classifier
                 done(L)
             for l in range(L - 1, -1, -1):
-                if proj and l == 0:                              # layer 0 with the qkv dgrad and the projection's gradients in its launch
+                if want and proj and l == 0:
+                    check(lib.vmc_tfam_layer0_bwd_proj_inputs(ctypes.byref(projp), wt_proj, ptr(mask), layers, ptr(ws), nbytes, *pdims, p_drop,
+                                                              seed_at(0), dt(dt16), stream()), "tfam_layer0_bwd_proj_inputs")
+                elif want and not proj:
+                    check(lib.vmc_tfam_layer_bwd_inputs(ptr(mask), ptr(mask_kv) if cross else None, layers, l, ptr(ws), nbytes, *dims, p_drop,
+                                                        seed_at(SEEDS_PER_LAYER * l), want, dt(dt16), stream()), "tfam_layer_bwd_inputs")
+                elif proj and l == 0:                            # layer 0 with the qkv dgrad and the projection's gradients in its launch
                     check(lib.vmc_tfam_layer0_bwd_proj(ctypes.byref(projp), ptr(mask), layers, ptr(ws), nbytes, *pdims, p_drop, seed_at(0),
                                                        dt(dt16), stream()), "tfam_layer0_bwd_proj")
                 else:
@@ -293,8 +342,21 @@ class TfamTrainFn(torch.autograd.Function):
                 if done is not None:
                     done(l)
         grads = tuple((fresh.get(id(p)) if p.requires_grad and getattr(p, "_vmc_grad", None) is None else None) for p in ctx.params)
+        gx = gm = None
+        if want:                                                 # views of the extension: they keep the buffer alive, ctx does not
+            B, T, Tk, D = dims[0], dims[1], dims[2], dims[3]
+            offs = (ctypes.c_longlong * 3)()
+            check(lib.vmc_tfam_train_input_grad_offsets(*dims, int(proj), offs), "tfam_train_input_grad_offsets")
+
+            def view(off, rows, cols):
+                return ws[off:off + rows * cols * 4].view(torch.float32).view(B, rows // B, cols)
+
+            if want & WANT_DX:
+                gx = view(offs[2], B * T, 2 * D) if proj else view(offs[0], B * T, D)
+            if want & WANT_DMOTION:
+                gm = view(offs[1], B * Tk, D)
         ctx.ws = None
-        return (None,) * 11 + grads
+        return (None, gx, gm) + (None,) * 8 + grads
 
 
 def _report(params):
@@ -312,10 +374,13 @@ def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None
     chain runs projection_layer in front of layer 0 (no cross attention; the projection draws no seed)."""
     B, T, _ = x.shape
     Tk = motion.shape[1] if cross else 0
+    inputs = x.requires_grad or (cross and motion.requires_grad)
+    if inputs and not (getattr(model, "fused_input_grads", False) and supported_inputs(model, B, T, Tk, cross, proj)):
+        return None
     if proj:
-        if cross or x.requires_grad or x.shape[-1] != 2 * model.d_model or not supported_proj(model, B, T):
+        if cross or x.shape[-1] != 2 * model.d_model or not supported_proj(model, B, T):
             return None
-    elif x.requires_grad or (cross and motion.requires_grad) or not supported(model, B, T, Tk, cross):
+    elif not supported(model, B, T, Tk, cross):
         return None
     p = float(model.layers[0].p)
     if any(float(layer.p) != p for layer in model.layers):
@@ -335,5 +400,5 @@ def forward_train(model, x, motion, mask, mask_kv, cross, seed_fn, pool_len=None
                 row[4], row[5], row[6] = seed_fn(), seed_fn(), seed_fn()
             seeds += row
         seeds.append(seed_fn() if p_mlp > 0.0 else 0)
-    tab = _tables(model, model.compute_dtype, cross, proj)
+    tab = _tables(model, model.compute_dtype, cross, proj, inputs=inputs and proj)
     return TfamTrainFn.apply(model, x, motion, mask, mask_kv, cross, p, p_mlp, tuple(seeds), pool_len, bool(proj), *tab.params())
