@@ -150,8 +150,11 @@ __device__ __forceinline__ void tn256_tile_body(const uint16_t* __restrict__ dY,
     oa[i] = (uint32_t)(row * lddy + ch * 8) * 2u;
     ob[i] = (uint32_t)(row * ldx + ch * 8) * 2u;
   }
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)dY, 0, (int)((size_t)M * lddy * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)((size_t)M * ldx * 2), 0x00020000);
+  // The descriptors end with the last element of the last token row, not M rows of ld elements: an operand may be a column window
+  // that ends where its parent tensor ends, and the unmasked loads of a ragged last tile (columns past N / K of row M - 1) would
+  // otherwise reach past that allocation.  Out of range they return zeros, into outputs that are never stored.
+  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)dY, 0, (int)(((size_t)(M - 1) * lddy + N) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)(((size_t)(M - 1) * ldx + K) * 2), 0x00020000);
   const uint32_t SA = 64u * (uint32_t)lddy * 2u, SB = 64u * (uint32_t)ldx * 2u;     // one 64-token stage
   const uint32_t pa0 = (uint32_t)s0 * SA + (uint32_t)n0 * 2u, pb0 = (uint32_t)s0 * SB + (uint32_t)k0 * 2u;
   const int wave_lds = wave * 1024;
