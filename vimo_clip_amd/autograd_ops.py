@@ -149,7 +149,9 @@ class _WgradQueue:
     gradient-ready hooks must fire -- and they leave as grouped launches (ops.wgrad_tn_group: every tile over all tokens, no slabs):
     when the queue is full, at the end of the backward pass (autograd engine callback) and, as a safety net, before the optimiser
     or a gradient norm reads the arena.  With gradient-ready hooks registered in a job of more than one rank (data-parallel bucket
-    exchange) a group leaves as soon as it fills one round of the chip, so that buckets still go out during the backward."""
+    exchange) a group leaves as soon as it fills one round of the chip, so that buckets still go out during the backward.
+    The parked problems belong to ONE graph task at a time; when the task changes in the middle of a pass (a nested engine pass, as
+    torch.utils.checkpoint runs) the parked list leaves as a launch of its own instead of being thrown away: see push()."""
     enabled = os.environ.get("VMC_WGRAD_GROUP", "1") != "0"       # builder A/B switch
     MAX_PROBLEMS = ops.WGRAD_GROUP_MAX      # 32: the 30 linears of a 4-layer TFAM step leave as one launch (480 tiles = 1.9 rounds)
     MAX_TILES = 1024
@@ -158,19 +160,30 @@ class _WgradQueue:
     def __init__(self):
         self.items = []
         self.tiles = 0
-        self._task = -1                 # autograd graph task (one per backward pass) whose end-of-pass callback is registered
+        self._task = -1                 # autograd graph task (one per backward pass) the parked problems belong to
+        self._armed = set()             # graph tasks whose end-of-pass callback is registered and has not run yet
 
     def push(self, dz, x, out, db, params):
         task = torch._C._current_graph_task_id()
         if task != self._task:
-            # first problem of a new backward pass.  Anything still parked belongs to a pass that raised before its callback ran:
-            # its slots are written again by this pass (two writers in one launch would race), so it is dropped
-            self.items, self.tiles, self._task = [], 0, task
-            if task >= 0:
-                torch.autograd.Variable._execution_engine.queue_callback(self._end_of_backward)
+            # The graph task changed while problems are parked.  Task ids grow, and a nested pass (a backward that runs an inner
+            # torch.autograd.backward, as torch.utils.checkpoint does) ends before the pass around it goes on.  So a parked list of a
+            # YOUNGER task than the current one belongs to an inner pass that never reached its callback: it raised, and is dropped.
+            # A list of an OLDER task is either the pass around this one, which is still running, or a pass that raised; the two cannot
+            # be told apart, so it leaves as a launch of its own before anything of this pass is parked (launches on one stream do not
+            # race: a stale problem's slot is simply written again by this pass).
+            if self.items and self._task > task >= 0:
+                self.items, self.tiles = [], 0
+            self.flush()
+            self._task = task
+        if task >= 0 and task not in self._armed:
+            self._armed = {t for t in self._armed if t < task}     # younger tasks that are still armed died without their callback
+            self._armed.add(task)
+            torch.autograd.Variable._execution_engine.queue_callback(lambda: self._end_of_backward(task))
         self.items.append((dz, x, out, db, params))
         self.tiles += ((dz.shape[1] + 255) // 256) * ((x.shape[1] + 255) // 256)
         if task < 0:                                   # not inside an engine-driven backward pass: nothing will call back
+            self._armed.clear()                        # ... and no pass is running, so none of them is waiting for its callback
             self.flush()
             return
         if len(self.items) >= self.MAX_PROBLEMS or self.tiles >= (self.MAX_TILES_OVERLAPPED if self._overlapping() else self.MAX_TILES):
@@ -183,7 +196,12 @@ class _WgradQueue:
         import torch.distributed as dist
         return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
 
-    def _end_of_backward(self):
+    def _end_of_backward(self, task):
+        self._armed = {t for t in self._armed if t < task}         # this task, and nested ones that died without their callback
+        if self._task != task:          # what is parked (if anything) is a younger, nested pass that raised: see push()
+            if self._task > task:
+                self.items, self.tiles, self._task = [], 0, -1
+            return
         self._task = -1
         self.flush()
 

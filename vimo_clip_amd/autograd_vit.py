@@ -3,6 +3,9 @@
 Same arithmetic as VisionTransformer._encode_patches, but every op is an autograd.Function from
 autograd_ops so that ``loss.backward()`` runs the hand-written backward kernels (K8).  Activations are
 kept in the compute dtype; the residual stream uses ``model.residual_dtype``.
+
+``model.recompute = "block"`` keeps only the input stream of every residual block for the backward pass and recomputes the block
+there (_BlockFn); ``saved_activation_bytes`` counts what either mode keeps.
 """
 from __future__ import annotations
 
@@ -18,6 +21,9 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
     through autograd, backward: the dgrad / wgrad GEMMs of those four linears shrink by N as well); the stream returned is then
     [F, D].  The attention of the last block still sees every token (its K / V gradients flow to all rows)."""
     dt16, D, H = model.compute_dtype, model.width, model.heads
+    recompute = getattr(model, "recompute", "none")
+    if recompute not in RECOMPUTE_MODES:
+        raise ValueError(f"VisionTransformer.recompute must be one of {RECOMPUTE_MODES}, got {recompute!r}")
     F = x.shape[0]
     g = model.input_resolution // model.patch_size
     N = g * g + 1
@@ -34,6 +40,10 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
         xs = ag.cast(xs, model.residual_dtype)
     blocks = list(model.transformer.resblocks)
     for i, blk in enumerate(blocks):
+        if recompute == "block":
+            xs = _BlockFn.apply(xs, (F, N, H, dt16, model.residual_dtype == torch.float32, cls_only and i + 1 == len(blocks)),
+                                *(blk.get_parameter(name) for name in _BLOCK_PARAMS))
+            continue
         h, xs = ag.layernorm(xs, blk.ln_1.weight, blk.ln_1.bias, dt16, passthrough=True)
         qkv = ag.linear(h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
         o = ag.SelfAttnPackedFn.apply(qkv, None, F, N, H)
@@ -46,6 +56,109 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
         xs = ag.linear(u, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, res=xs,
                        out_f32=(model.residual_dtype == torch.float32))
     return xs, F, N, cls_only
+
+
+RECOMPUTE_MODES = ("none", "block")
+_BLOCK_PARAMS = ("ln_1.weight", "ln_1.bias", "attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias",
+                 "ln_2.weight", "ln_2.bias", "mlp.c_fc.weight", "mlp.c_fc.bias", "mlp.c_proj.weight", "mlp.c_proj.bias")
+
+
+class _Ctx:
+    """What a per-op Function's forward and backward use of their ``ctx``, without an autograd node behind it: _BlockFn runs the
+    Functions' static methods itself, in the order the engine runs the nodes of the same block."""
+
+    def __init__(self, *needs_input_grad):
+        self.needs_input_grad = needs_input_grad
+        self.saved_tensors = ()
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+
+def _block_forward(xs, meta, params, keep):
+    """One residual block through the same Function bodies, with the same arguments, as the loop of vit_tokens_train (the training
+    launches: weight copies made with ``both=True``, the c_fc pre-activation written as a side output).  keep: return the contexts
+    the backward needs; otherwise they die here, and with them everything but the block's output."""
+    F, N, H, dt16, out_f32, cls = meta
+    ln1_w, ln1_b, in_w, in_b, out_w, out_b, ln2_w, ln2_b, fc_w, fc_b, proj_w, proj_b = params
+    c = {k: _Ctx(*need) for k, need in (("ln_1", (True,)), ("in_proj", (True,)), ("attn", (True,)), ("cls_o", (True,)), ("cls_x", (True,)),
+                                        ("out_proj", (True, True, True, True)), ("ln_2", (True,)), ("c_fc", (True,)),
+                                        ("c_proj", (True, True, True, True)))}
+    h, xs = ag.LayerNormFn.forward(c["ln_1"], xs, ln1_w, ln1_b, dt16, True, False)
+    qkv = ag.LinearFn.forward(c["in_proj"], h, in_w, in_b, None, ag.ACT_NONE, False)
+    o = ag.SelfAttnPackedFn.forward(c["attn"], qkv, None, F, N, H)
+    if cls:
+        o, xs = _ClsRowsFn.forward(c["cls_o"], o, F, N), _ClsRowsFn.forward(c["cls_x"], xs, F, N)
+    xs = ag.LinearFn.forward(c["out_proj"], o, out_w, out_b, xs, ag.ACT_NONE, out_f32)
+    h, xs = ag.LayerNormFn.forward(c["ln_2"], xs, ln2_w, ln2_b, dt16, True, False)
+    u = ag.LinearFn.forward(c["c_fc"], h, fc_w, fc_b, None, ops.ACT_QUICKGELU, False)
+    xs = ag.LinearFn.forward(c["c_proj"], u, proj_w, proj_b, xs, ag.ACT_NONE, out_f32)
+    return (xs, c) if keep else (xs, None)
+
+
+class _BlockFn(torch.autograd.Function):
+    """A residual block as ONE autograd node that saves its input stream only (``model.recompute = "block"``).  The backward runs the
+    block's forward again from that input and then the backward bodies of the per-op Functions, in the engine's order for the same
+    block: the kernels and their operands are those of the per-op path, so outputs and gradients are the same bits.  The weight
+    gradients are parked in the surrounding pass's wgrad_queue (no nested engine pass) and leave at the end of the block, and the
+    16-bit weight copies are the cached ones of the first forward (nothing has stepped in between)."""
+
+    @staticmethod
+    def forward(ctx, xs, meta, *params):
+        ctx.save_for_backward(xs)
+        ctx.meta, ctx.params = meta, params
+        return _block_forward(xs, meta, params, keep=False)[0]
+
+    @staticmethod
+    def backward(ctx, dy):
+        (xs,) = ctx.saved_tensors
+        cls = ctx.meta[5]
+        _, c = _block_forward(xs, ctx.meta, ctx.params, keep=True)
+        g = [None] * 12                                 # gradients of _BLOCK_PARAMS that are not written into an arena slot
+        du, g[10], g[11], dres = ag.LinearFn.backward(c.pop("c_proj"), dy)[:4]
+        dh, g[8], g[9] = ag.LinearFn.backward(c.pop("c_fc"), du)[:3]
+        dxs, g[6], g[7] = ag.LayerNormFn.backward(c.pop("ln_2"), dh, dres)[:3]
+        do, g[4], g[5], dres = ag.LinearFn.backward(c.pop("out_proj"), dxs)[:4]
+        if cls:
+            dres = _ClsRowsFn.backward(c.pop("cls_x"), dres)[0]
+            do = _ClsRowsFn.backward(c.pop("cls_o"), do)[0]
+        dqkv = ag.SelfAttnPackedFn.backward(c.pop("attn"), do)[0]
+        dh, g[2], g[3] = ag.LinearFn.backward(c.pop("in_proj"), dqkv)[:3]
+        dx, g[0], g[1] = ag.LayerNormFn.backward(c.pop("ln_1"), dh, dres)[:3]
+        # the parked weight-gradient problems hold this block's recomputed activations and their gradients (32 D bytes per row): they
+        # leave now, as one group per block, so that nothing of a recomputed block outlives its backward.  A tile's arithmetic does
+        # not depend on what shares its launch, so the gradients are the bits of the larger groups of the per-op path
+        ag.wgrad_queue.flush()
+        return (dx, None, *g)
+
+
+def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes16: int = 2, residual_bytes: int = 4,
+                           cls_only: bool = True) -> int:
+    """Bytes the residual blocks of the training forward keep for the backward pass (what the per-op Functions of autograd_ops
+    hand to ``save_for_backward``; the patch GEMM, ln_pre, ln_post and the projection are not counted).
+    geometry: a model name or (resolution, patch, width, layers, heads, output_dim).
+    "none": per token row and block the residual stream at ln_1 and at ln_2, the two LayerNorm outputs, qkv, the attention output,
+    the c_fc pre-activation and the QuickGELU output -- (2 r + 14 b) D bytes (36 D for fp32 / 16-bit) -- plus lse (4 H) and two
+    (mean, rstd) pairs (16).  With cls_only the last block keeps everything after its attention for the F class rows only.
+    "block": one input stream per block, r D bytes per row.  During the backward one recomputed block ("none" with one layer, the
+    last block's class-row shortcut aside) is alive on top of that."""
+    if recompute not in RECOMPUTE_MODES:
+        raise ValueError(f"recompute must be one of {RECOMPUTE_MODES}, got {recompute!r}")
+    if isinstance(geometry, str):
+        from .synth import vit_geometry
+        geometry = vit_geometry(geometry)
+    R, p, D, L, H, _E = geometry
+    N = (R // p) ** 2 + 1
+    rows, r, b = frames * N, residual_bytes, bytes16
+    if recompute == "block":
+        return L * rows * r * D
+    attn_half = (r + 5 * b) * D + 4 * H + 8          # stream at ln_1, ln_1 output, qkv, attention output; lse; (mean, rstd)
+    mlp_half = (r + 9 * b) * D + 8                   # stream at ln_2, ln_2 output, z, u; (mean, rstd)
+    full = rows * (attn_half + mlp_half)
+    if not cls_only:
+        return L * full
+    # the last block: out_proj reads a gathered copy of the class rows of the attention output (one more 16-bit row), then F rows
+    return (L - 1) * full + rows * attn_half + frames * (b * D + mlp_half)
 
 
 class _ClsRowsFn(torch.autograd.Function):

@@ -100,6 +100,9 @@ class VisionTransformer(nn.Module):
         # branch that has left the caches -- off by default (profiles/README.md, round 2)
         self.defer_attn_add = False
         self.exact_patch_embed = True   # split-precision patch GEMM (fp32-accurate; +0.2 % FLOPs): see patch_operands()
+        # training forward: "block" saves one input stream per residual block and recomputes the block in the backward pass
+        # (autograd_vit._BlockFn: same bits, 4 D instead of 36 D bytes per token row and block); "none" saves every intermediate
+        self.recompute = "none"
         self.frame_chunk = 256  # frames per pass (bounds activation memory; F*N*4D*2 B for the MLP buffer)
         self._init_weights()
 

@@ -71,12 +71,15 @@ class ResidualMLP(nn.Module):
 
 class FlowStudentModel(nn.Module):
     def __init__(self, clip_model_name="ViT-B/32", device="cuda", num_classes=140, alpha=0.1,
-                 compute_dtype=torch.bfloat16, residual_dtype=torch.float32):
+                 compute_dtype=torch.bfloat16, residual_dtype=torch.float32, recompute="none"):
+        """recompute: "none" or "block" (VisionTransformer.recompute: the training forward keeps one stream per block and
+        recomputes the block in the backward pass; same results, a fraction of the activation memory)."""
         super().__init__()
         self.device = device
         self.compute_dtype = compute_dtype
         self.visual_encoder = VisionTransformer.from_name(clip_model_name, compute_dtype=compute_dtype,
                                                           residual_dtype=residual_dtype)
+        self.visual_encoder.recompute = recompute
         self.preprocess = _Preprocess(self.visual_encoder.input_resolution)
         embed_dim = self.visual_encoder.output_dim
         self.residual_mlp = ResidualMLP(embed_dim, alpha=alpha, compute_dtype=compute_dtype)

@@ -77,7 +77,8 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     else:
         train_set = SyntheticSegmentDataset(args.synthetic, args.sequence_length, E, args.num_classes, seed=3)
         val_set = SyntheticSegmentDataset(max(args.batch_size * world, args.synthetic // 8), args.sequence_length, E, args.num_classes, seed=4)
-    model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha)
+    model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha,
+                             recompute=getattr(args, "recompute", "none"))
     arena = GradArena(model.parameters())
     parallel.broadcast_parameters(arena.flat_param)
     optimizer = FusedAdam(arena, lr=args.learning_rate)
@@ -125,6 +126,8 @@ if __name__ == "__main__":
     p.add_argument("--grad_clip_norm", type=float, default=None)
     p.add_argument("--checkpoint_dir", default=None, help="write student_epoch_N.pth here and student_best.pth into '<dir> - best' "
                                                            "(the reference uses checkpoints/<timestamp>); omitted = no files")
+    p.add_argument("--recompute", default="none", choices=["none", "block"],
+                   help="block: keep one residual stream per transformer block and recompute the block in the backward pass")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

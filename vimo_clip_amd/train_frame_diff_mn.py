@@ -33,6 +33,8 @@ def build_parser() -> argparse.ArgumentParser:
     arg("spatial_size", type=int, nargs=2, default=(224, 224), metavar=("H", "W"))
     arg("clip_model_name", default="ViT-B/32")
     arg("checkpoint_dir", default=None)
+    arg("recompute", default="none", choices=["none", "block"],
+        help="block: keep one residual stream per transformer block and recompute the block in the backward pass")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
