@@ -294,14 +294,37 @@ class VisionTransformer(nn.Module):
             self.w16(pre + "c_proj", blk.mlp.c_proj.weight)
         self.w16("proj", self.proj, transposed=True)
 
+    def _patches(self, x: torch.Tensor, wrap: bool = False):
+        """u8 frames [F,3,R,R], u8 grey planes [F,1,R,R] or normalised float pixel values [F,3,R,R] -> (patch operand of the
+        patch-embedding GEMM, its ``patch_mode`` for ``patch_operands``)."""
+        p, dt16 = self.patch_size, self.compute_dtype
+        if x.dtype != torch.uint8:
+            if self.exact_patch_embed:
+                return ops.patches_f32_split(x, p, dt16), "f32_split"
+            return ops.patches_f32(x, p, dt16), "plain"
+        gray = x.shape[1] == 1
+        if self.exact_patch_embed:
+            return (ops.patches_gray_u8_exact if gray else ops.patches_u8_exact)(x, p, dt16, wrap), "u8_exact"
+        return (ops.preprocess_patches_gray_u8 if gray else ops.preprocess_patches_u8)(x, p, dt16, wrap), "plain"
+
+    def _encode_chunks(self, x: torch.Tensor, wrap_quirk: bool = False, crop_mode: str = "torchvision") -> torch.Tensor:
+        """``frame_chunk`` frames at a time: resize / crop (u8 frames only), patch extraction, encoder."""
+        outs = []
+        for s in range(0, x.shape[0], self.frame_chunk):
+            fr, wrap = x[s:s + self.frame_chunk], False
+            if fr.dtype == torch.uint8:
+                fr, wrap = self.fit_frames_u8(fr, wrap_quirk, crop_mode)
+            patches, mode = self._patches(fr, wrap)
+            outs.append(self._encode_patches(patches, fr.shape[0], patch_mode=mode))
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
     @torch.no_grad()
     def _encode_on_streams(self, frames_u8: torch.Tensor, wrap: bool, n: int) -> torch.Tensor:
         """The frames of one pass as n slices on n streams: while one slice's kernel drains (the last round of a persistent GEMM walk,
         the tail launch, a memory-bound pass that leaves the MFMA pipes idle) another slice's next kernel already runs.  Frames are
         independent and every slice runs the same kernels: same bits as one stream (tests/test_gpu_encoder.py)."""
         F = frames_u8.shape[0]
-        mode = "u8_exact" if self.exact_patch_embed else "plain"
-        self._warm_weight_copies(mode)
+        self._warm_weight_copies("u8_exact" if self.exact_patch_embed else "plain")
         cur = torch.cuda.current_stream()
         pool = getattr(self, "_slice_streams", None)
         if pool is None or len(pool) < n:
@@ -311,11 +334,7 @@ class VisionTransformer(nn.Module):
         for st, a, b in zip(pool, cuts[:-1], cuts[1:]):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                fr = frames_u8[a:b]
-                if self.exact_patch_embed:
-                    patches = ops.patches_u8_exact(fr, self.patch_size, self.compute_dtype, wrap)
-                else:
-                    patches = ops.preprocess_patches_u8(fr, self.patch_size, self.compute_dtype, wrap)
+                patches, mode = self._patches(frames_u8[a:b], wrap)
                 outs.append(self._encode_patches(patches, b - a, patch_mode=mode))
         for st in pool[:n]:
             cur.wait_stream(st)
@@ -328,16 +347,7 @@ class VisionTransformer(nn.Module):
         if n > 1 and frames_u8.is_cuda and 64 * n <= frames_u8.shape[0] <= self.frame_chunk:
             fr, wrap = self.fit_frames_u8(frames_u8, wrap_quirk, crop_mode)
             return self._encode_on_streams(fr, wrap, n)
-        outs = []
-        for s in range(0, frames_u8.shape[0], self.frame_chunk):
-            fr, wrap = self.fit_frames_u8(frames_u8[s:s + self.frame_chunk], wrap_quirk, crop_mode)
-            if self.exact_patch_embed:
-                patches = ops.patches_u8_exact(fr, self.patch_size, self.compute_dtype, wrap)
-                outs.append(self._encode_patches(patches, fr.shape[0], patch_mode="u8_exact"))
-            else:
-                patches = ops.preprocess_patches_u8(fr, self.patch_size, self.compute_dtype, wrap)
-                outs.append(self._encode_patches(patches, fr.shape[0]))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return self._encode_chunks(frames_u8, wrap_quirk, crop_mode)
 
     @torch.no_grad()
     def encode_gray_u8(self, gray_u8: torch.Tensor, wrap_quirk: bool = False, crop_mode: str = "torchvision") -> torch.Tensor:
@@ -345,29 +355,12 @@ class VisionTransformer(nn.Module):
         resize / crop and a third of the bytes read by patch extraction (frame-difference motion frames, ops.frame_diff_gray)."""
         if gray_u8.dim() != 4 or gray_u8.shape[1] != 1 or gray_u8.dtype != torch.uint8:
             raise ValueError("gray frames must be u8 [F,1,H,W]")
-        outs = []
-        for s in range(0, gray_u8.shape[0], self.frame_chunk):
-            fr, wrap = self.fit_frames_u8(gray_u8[s:s + self.frame_chunk], wrap_quirk, crop_mode)
-            if self.exact_patch_embed:
-                patches = ops.patches_gray_u8_exact(fr, self.patch_size, self.compute_dtype, wrap)
-                outs.append(self._encode_patches(patches, fr.shape[0], patch_mode="u8_exact"))
-            else:
-                patches = ops.preprocess_patches_gray_u8(fr, self.patch_size, self.compute_dtype, wrap)
-                outs.append(self._encode_patches(patches, fr.shape[0]))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return self._encode_chunks(gray_u8, wrap_quirk, crop_mode)
 
     @torch.no_grad()
     def encode_pixel_values(self, pixel_values: torch.Tensor) -> torch.Tensor:
         """[F,3,R,R] normalised floats -> [F,E] f32 (the ``visual_encoder(x)`` call of student_model.py:84)."""
-        outs = []
-        for s in range(0, pixel_values.shape[0], self.frame_chunk):
-            pv = pixel_values[s:s + self.frame_chunk]
-            if self.exact_patch_embed:
-                outs.append(self._encode_patches(ops.patches_f32_split(pv, self.patch_size, self.compute_dtype), pv.shape[0],
-                                                 patch_mode="f32_split"))
-            else:
-                outs.append(self._encode_patches(ops.patches_f32(pv, self.patch_size, self.compute_dtype), pv.shape[0]))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        return self._encode_chunks(pixel_values)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -1,4 +1,6 @@
 // HBM-bound helper kernels: frame preprocess + patch extraction, casts, transposes, pooling (gfx950).
+#include <type_traits>
+
 #include "common.h"
 
 extern "C" int vmc_abi_version(void) { return 1; }
@@ -14,15 +16,38 @@ extern "C" const char* vmc_error_string(int code) {
   }
 }
 
-// ---- K0: u8 NCHW frames -> normalised 16-bit patch matrix --------------------------------------
-// One thread per 4 consecutive pixels of one (frame, channel, row): coalesced 4-byte reads; the four
-// results land in (at most two) patch rows.
-template <typename T>
-__global__ void __launch_bounds__(256) preprocess_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
-                                                         int F, int R, int p, int kpad, int wrap) {
+// ---- K0: frames -> 16-bit patch matrix (the six patch entries of include/vmc.h) -----------------------------------------------
+// One kernel over the 16-bit type, the layout of a patch row and the source channel count (3, or 1: a grey plane written into the
+// three channel slices, a third of the bytes read).  Layouts:
+//   PATCH_NORM_U8    u8 pixels  -> [kpad]    ((v / 255) - mean_c) / std_c
+//   PATCH_RAW_F32    f32 pixels -> [kpad]    x
+//   PATCH_EXACT_U8   u8 pixels  -> [2 kpad]  [v | v], the raw pixel 0..255 (exact in 16 bits)
+//   PATCH_SPLIT_F32  f32 pixels -> [3 kpad]  [x_hi | x_lo | x_hi], x_lo = x - x_hi
+// The last two are the split-precision operands of the inference patch-embedding GEMM: it is 0.2 % of the encoder's FLOPs but its
+// 16-bit operand rounding was the largest single contribution to the embedding error (tests/test_gpu_encoder.py per-stage trace:
+// the stream error right after ln_pre was 60-75 % of the final one).  Two extra K slices make that GEMM fp32-accurate:
+//   u8 frames:   A = [v | v],  W = [W'_hi | W'_lo],  W' = W / std_c,  bias' = -255 sum_k W mean_c / std_c,  alpha = 1/255
+//                ->  alpha (A W^T + bias') = sum_k ((v/255 - mean)/std) W
+//   f32 pixels:  A = [x_hi | x_lo | x_hi],  W = [W_hi | W_hi | W_lo]   (the product's cross terms)
+enum PatchLayout { PATCH_NORM_U8, PATCH_RAW_F32, PATCH_EXACT_U8, PATCH_SPLIT_F32 };
+template <PatchLayout LAYOUT>
+using patch_src_t = std::conditional_t<LAYOUT == PATCH_RAW_F32 || LAYOUT == PATCH_SPLIT_F32, float, uint8_t>;
+template <PatchLayout LAYOUT>
+constexpr int patch_parts = LAYOUT == PATCH_EXACT_U8 ? 2 : LAYOUT == PATCH_SPLIT_F32 ? 3 : 1;
+
+// One thread per 4 consecutive pixels of one (frame, source channel, row): one coalesced 4- or 16-byte read; the four results
+// land in (at most two) patch rows.
+template <typename T, PatchLayout LAYOUT, int CH>
+__global__ void __launch_bounds__(256) patch_kernel(const void* __restrict__ pixels, uint16_t* __restrict__ patches, int F, int R, int p,
+                                                    int kpad, int wrap) {
+  const patch_src_t<LAYOUT>* __restrict__ src = (const patch_src_t<LAYOUT>*)pixels;
+  constexpr bool f32 = std::is_same_v<patch_src_t<LAYOUT>, float>;
+  constexpr int parts = patch_parts<LAYOUT>;
+  constexpr int nc = CH == 1 ? 3 : 1;        // channel slices a thread writes: c0 + 0 .. c0 + nc - 1, a compile-time trip count
+                                             // (a loop from c0 to c0 + nc costs the RGB kernels extra 64-bit address adds)
   const int g = R / p;
   const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * 3 * R * quads_per_row;
+  const size_t total = (size_t)F * CH * R * quads_per_row;
   const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
   const float istd[3] = {1.0f / 0.26862954f, 1.0f / 0.26130258f, 1.0f / 0.27577711f};
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -30,24 +55,69 @@ __global__ void __launch_bounds__(256) preprocess_kernel(const uint8_t* __restri
     size_t t = i / quads_per_row;
     const int y = (int)(t % R);
     t /= R;
-    const int c = (int)(t % 3);
-    const int f = (int)(t / 3);
-    const uint32_t px = *(const uint32_t*)(frames + i * 4);
+    const int c0 = (int)(t % CH);
+    const int f = (int)(t / CH);
     const int py = y / p, dy = y % p;
+    std::conditional_t<f32, float, uint32_t> v[4];
+    if constexpr (f32) {
+      const float4 px = *(const float4*)(src + i * 4);
+      v[0] = px.x, v[1] = px.y, v[2] = px.z, v[3] = px.w;
+    } else {
+      const uint32_t px = *(const uint32_t*)(src + i * 4);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      uint32_t v = (px >> (8 * j)) & 0xFFu;
-      if (wrap) v = (256u - v) & 0xFFu;
-      // same operation order as ToTensor (/255) then Normalize ((x - mean) / std)
-      const float val = ((float)v / 255.0f - mean[c]) * istd[c];
+      for (int j = 0; j < 4; ++j) {
+        v[j] = (px >> (8 * j)) & 0xFFu;
+        if (wrap) v[j] = (256u - v[j]) & 0xFFu;
+      }
+    }
+    auto at = [&](int x, int c) {        // where pixel x of this row goes in channel slice c of its patch row
       const int pxi = x / p, dx = x % p;
       const size_t prow = ((size_t)f * g + py) * g + pxi;
-      patches[prow * kpad + (c * p + dy) * p + dx] = T::from_f32(val);
+      return patches + prow * (parts * (size_t)kpad) + (c * p + dy) * p + dx;
+    };
+    if constexpr (LAYOUT == PATCH_EXACT_U8) {
+      if ((p & 1) == 0) {      // even patch size (14 / 16 / 32): a pixel pair at an even x never straddles a patch -> 4-byte stores
+#pragma unroll
+        for (int j = 0; j < 4; j += 2) {
+          const uint32_t h2 = (uint32_t)T::from_f32((float)v[j]) | ((uint32_t)T::from_f32((float)v[j + 1]) << 16);
+#pragma unroll
+          for (int k = 0; k < nc; ++k) {
+            uint16_t* dst = at(xq * 4 + j, c0 + k);
+            *(uint32_t*)dst = h2;
+            *(uint32_t*)(dst + kpad) = h2;
+          }
+        }
+        continue;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int k = 0; k < nc; ++k) {
+        const int c = c0 + k;
+        uint16_t* dst = at(xq * 4 + j, c);
+        if constexpr (LAYOUT == PATCH_NORM_U8) {
+          // same operation order as ToTensor (/255) then Normalize ((x - mean) / std)
+          dst[0] = T::from_f32(((float)v[j] / 255.0f - mean[c]) * istd[c]);
+        } else if constexpr (LAYOUT == PATCH_RAW_F32) {
+          dst[0] = T::from_f32(v[j]);
+        } else if constexpr (LAYOUT == PATCH_EXACT_U8) {
+          const uint16_t h = T::from_f32((float)v[j]);              // integers <= 255 are exact in bf16 and f16
+          dst[0] = h;
+          dst[kpad] = h;
+        } else {
+          const uint16_t hi = T::from_f32(v[j]);
+          const uint16_t lo = T::from_f32(v[j] - T::to_f32(hi));
+          dst[0] = hi;
+          dst[kpad] = lo;
+          dst[2 * kpad] = hi;
+        }
+      }
     }
   }
 }
 
+// Zeroes columns [k, kpad) of every kpad-wide row (a patch row of several parts is that many rows).
 __global__ void zero_pad_cols_kernel(uint16_t* __restrict__ patches, size_t rows, int k, int kpad) {
   const int padw = kpad - k;
   const size_t total = rows * padw;
@@ -55,343 +125,51 @@ __global__ void zero_pad_cols_kernel(uint16_t* __restrict__ patches, size_t rows
     patches[(i / padw) * kpad + k + (i % padw)] = 0;
 }
 
+template <PatchLayout LAYOUT, int CH>
+static int launch_patches(const patch_src_t<LAYOUT>* src, void* patches, int F, int R, int p, int kpad, int wrap, int dtype16,
+                          void* stream) {
+  constexpr int parts = patch_parts<LAYOUT>;
+  if (!src || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
+  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
+  if ((uintptr_t)src & (4 * sizeof(*src) - 1)) return VMC_E_ALIGN;        // a thread's one load of four pixels
+  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
+  hipStream_t s = (hipStream_t)stream;
+  const int k = 3 * p * p;
+  if (kpad > k) {
+    const size_t rows = (size_t)F * (R / p) * (R / p) * parts;
+    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
+    VMC_CHECK_LAUNCH();
+  }
+  const size_t total = (size_t)F * CH * R * (R / 4);
+  const auto kernel = dtype16 == VMC_BF16 ? patch_kernel<BF16, LAYOUT, CH> : patch_kernel<F16, LAYOUT, CH>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, (const void*)src, (uint16_t*)patches, F, R, p, kpad, wrap);
+  VMC_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int vmc_preprocess_patches_u8(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk,
                                          int dtype16, void* stream) {
-  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * 3 * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(preprocess_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(preprocess_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return launch_patches<PATCH_NORM_U8, 3>(frames, patches, F, R, p, kpad, wrap_quirk, dtype16, stream);
 }
-
-// Grey frames u8 [F,1,R,R] -> the patch matrix vmc_preprocess_patches_u8 writes for the same plane given three times: a thread
-// reads its 4 pixels once and writes them into the three channel slices of the patch row (a third of the bytes read).
-template <typename T>
-__global__ void __launch_bounds__(256) preprocess_gray_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
-                                                              int F, int R, int p, int kpad, int wrap) {
-  const int g = R / p;
-  const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * R * quads_per_row;
-  const float mean[3] = {0.48145466f, 0.4578275f, 0.40821073f};
-  const float istd[3] = {1.0f / 0.26862954f, 1.0f / 0.26130258f, 1.0f / 0.27577711f};
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int xq = (int)(i % quads_per_row);
-    const size_t t = i / quads_per_row;
-    const int y = (int)(t % R);
-    const int f = (int)(t / R);
-    const uint32_t px = *(const uint32_t*)(frames + i * 4);
-    const int py = y / p, dy = y % p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      uint32_t v = (px >> (8 * j)) & 0xFFu;
-      if (wrap) v = (256u - v) & 0xFFu;
-      const int pxi = x / p, dx = x % p;
-      const size_t prow = ((size_t)f * g + py) * g + pxi;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float val = ((float)v / 255.0f - mean[c]) * istd[c];      // the expression of preprocess_kernel
-        patches[prow * kpad + (c * p + dy) * p + dx] = T::from_f32(val);
-      }
-    }
-  }
-}
-
 extern "C" int vmc_preprocess_patches_gray_u8(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk,
                                               int dtype16, void* stream) {
-  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(preprocess_gray_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(preprocess_gray_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return launch_patches<PATCH_NORM_U8, 1>(frames, patches, F, R, p, kpad, wrap_quirk, dtype16, stream);
 }
-
-// Same patch extraction for frames that are already normalised floats (HF `pixel_values`, the
-// argument of CLIPModel.get_image_features at extract_embeddings.py:94).
-template <typename T>
-__global__ void __launch_bounds__(256) patches_f32_kernel(const float* __restrict__ pix, uint16_t* __restrict__ patches, int F, int R,
-                                                          int p, int kpad) {
-  const int g = R / p;
-  const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * 3 * R * quads_per_row;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int xq = (int)(i % quads_per_row);
-    size_t t = i / quads_per_row;
-    const int y = (int)(t % R);
-    t /= R;
-    const int c = (int)(t % 3);
-    const int f = (int)(t / 3);
-    const float4 px = *(const float4*)(pix + i * 4);
-    const float v[4] = {px.x, px.y, px.z, px.w};
-    const int py = y / p, dy = y % p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      const int pxi = x / p, dx = x % p;
-      const size_t prow = ((size_t)f * g + py) * g + pxi;
-      patches[prow * kpad + (c * p + dy) * p + dx] = T::from_f32(v[j]);
-    }
-  }
-}
-
-extern "C" int vmc_patches_f32(const float* pixel_values, void* patches, int F, int R, int p, int kpad, int dtype16, void* stream) {
-  if (!pixel_values || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)pixel_values & 15) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * 3 * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(patches_f32_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, pixel_values, (uint16_t*)patches, F, R, p, kpad);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(patches_f32_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, pixel_values, (uint16_t*)patches, F, R, p, kpad);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
-// ---- split-precision patch operands (inference): the patch-embedding GEMM is 0.2 % of the encoder's FLOPs but its 16-bit
-// operand rounding was the largest single contribution to the embedding error (tests/test_gpu_encoder.py per-stage trace: the
-// stream error right after ln_pre was 60-75 % of the final one).  Two extra K slices make that GEMM fp32-accurate:
-//   u8 frames:   A = [v | v]            (v = raw pixel 0..255, exact in 16 bits),  W = [W'_hi | W'_lo],  W' = W / std_c,
-//                bias' = -255 sum_k W mean_c / std_c,  alpha = 1/255   ->  alpha (A W^T + bias') = sum_k ((v/255 - mean)/std) W
-//   f32 pixels:  A = [x_hi | x_lo | x_hi],  W = [W_hi | W_hi | W_lo]   (x_lo = x - x_hi: the product's cross terms)
-template <typename T>
-__global__ void __launch_bounds__(256) patches_u8_exact_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
-                                                               int F, int R, int p, int kpad, int wrap) {
-  const int g = R / p;
-  const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * 3 * R * quads_per_row;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int xq = (int)(i % quads_per_row);
-    size_t t = i / quads_per_row;
-    const int y = (int)(t % R);
-    t /= R;
-    const int c = (int)(t % 3);
-    const int f = (int)(t / 3);
-    const uint32_t px = *(const uint32_t*)(frames + i * 4);
-    const int py = y / p, dy = y % p;
-    if ((p & 1) == 0) {        // even patch size (14 / 16 / 32): a pixel pair at an even x never straddles a patch -> 4-byte stores
-#pragma unroll
-      for (int j = 0; j < 4; j += 2) {
-        const int x = xq * 4 + j;
-        uint32_t v0 = (px >> (8 * j)) & 0xFFu, v1 = (px >> (8 * j + 8)) & 0xFFu;
-        if (wrap) { v0 = (256u - v0) & 0xFFu; v1 = (256u - v1) & 0xFFu; }
-        const int pxi = x / p, dx = x % p;
-        const size_t prow = ((size_t)f * g + py) * g + pxi;
-        const uint32_t h2 = (uint32_t)T::from_f32((float)v0) | ((uint32_t)T::from_f32((float)v1) << 16);
-        uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
-        *(uint32_t*)dst = h2;
-        *(uint32_t*)(dst + kpad) = h2;
-      }
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      uint32_t v = (px >> (8 * j)) & 0xFFu;
-      if (wrap) v = (256u - v) & 0xFFu;
-      const int pxi = x / p, dx = x % p;
-      const size_t prow = ((size_t)f * g + py) * g + pxi;
-      const uint16_t h = T::from_f32((float)v);              // integers <= 255 are exact in bf16 and f16
-      uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
-      dst[0] = h;
-      dst[kpad] = h;
-    }
-  }
-}
-
-template <typename T>
-__global__ void __launch_bounds__(256) patches_f32_split_kernel(const float* __restrict__ pix, uint16_t* __restrict__ patches, int F, int R,
-                                                                int p, int kpad) {
-  const int g = R / p;
-  const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * 3 * R * quads_per_row;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int xq = (int)(i % quads_per_row);
-    size_t t = i / quads_per_row;
-    const int y = (int)(t % R);
-    t /= R;
-    const int c = (int)(t % 3);
-    const int f = (int)(t / 3);
-    const float4 px = *(const float4*)(pix + i * 4);
-    const float v[4] = {px.x, px.y, px.z, px.w};
-    const int py = y / p, dy = y % p;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      const int pxi = x / p, dx = x % p;
-      const size_t prow = ((size_t)f * g + py) * g + pxi;
-      const uint16_t hi = T::from_f32(v[j]);
-      const uint16_t lo = T::from_f32(v[j] - T::to_f32(hi));
-      uint16_t* dst = patches + prow * (3 * (size_t)kpad) + (c * p + dy) * p + dx;
-      dst[0] = hi;
-      dst[kpad] = lo;
-      dst[2 * kpad] = hi;
-    }
-  }
-}
-
-__global__ void zero_pad_cols_multi_kernel(uint16_t* __restrict__ patches, size_t rows, int k, int kpad, int parts) {
-  const int padw = kpad - k;
-  const size_t total = rows * padw * parts;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t row = i / ((size_t)padw * parts);
-    const int rem = (int)(i % ((size_t)padw * parts));
-    patches[row * ((size_t)kpad * parts) + (size_t)(rem / padw) * kpad + k + (rem % padw)] = 0;
-  }
-}
-
 extern "C" int vmc_patches_u8_exact(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk, int dtype16,
                                     void* stream) {
-  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * 3 * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_multi_kernel, dim3(grid_for(rows * (kpad - k) * 2, 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad, 2);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(patches_u8_exact_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(patches_u8_exact_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return launch_patches<PATCH_EXACT_U8, 3>(frames, patches, F, R, p, kpad, wrap_quirk, dtype16, stream);
 }
-
-// vmc_patches_u8_exact for grey frames u8 [F,1,R,R]: the bytes it writes for the same plane given three times.
-template <typename T>
-__global__ void __launch_bounds__(256) patches_gray_u8_exact_kernel(const uint8_t* __restrict__ frames, uint16_t* __restrict__ patches,
-                                                                    int F, int R, int p, int kpad, int wrap) {
-  const int g = R / p;
-  const int quads_per_row = R >> 2;
-  const size_t total = (size_t)F * R * quads_per_row;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int xq = (int)(i % quads_per_row);
-    const size_t t = i / quads_per_row;
-    const int y = (int)(t % R);
-    const int f = (int)(t / R);
-    const uint32_t px = *(const uint32_t*)(frames + i * 4);
-    const int py = y / p, dy = y % p;
-    if ((p & 1) == 0) {        // even patch size: pixel pairs never straddle a patch -> 4-byte stores (as patches_u8_exact_kernel)
-#pragma unroll
-      for (int j = 0; j < 4; j += 2) {
-        const int x = xq * 4 + j;
-        uint32_t v0 = (px >> (8 * j)) & 0xFFu, v1 = (px >> (8 * j + 8)) & 0xFFu;
-        if (wrap) { v0 = (256u - v0) & 0xFFu; v1 = (256u - v1) & 0xFFu; }
-        const int pxi = x / p, dx = x % p;
-        const size_t prow = ((size_t)f * g + py) * g + pxi;
-        const uint32_t h2 = (uint32_t)T::from_f32((float)v0) | ((uint32_t)T::from_f32((float)v1) << 16);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
-          *(uint32_t*)dst = h2;
-          *(uint32_t*)(dst + kpad) = h2;
-        }
-      }
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = xq * 4 + j;
-      uint32_t v = (px >> (8 * j)) & 0xFFu;
-      if (wrap) v = (256u - v) & 0xFFu;
-      const int pxi = x / p, dx = x % p;
-      const size_t prow = ((size_t)f * g + py) * g + pxi;
-      const uint16_t h = T::from_f32((float)v);              // integers <= 255 are exact in bf16 and f16
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        uint16_t* dst = patches + prow * (2 * (size_t)kpad) + (c * p + dy) * p + dx;
-        dst[0] = h;
-        dst[kpad] = h;
-      }
-    }
-  }
-}
-
 extern "C" int vmc_patches_gray_u8_exact(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk, int dtype16,
                                          void* stream) {
-  if (!frames || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)frames & 3) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_multi_kernel, dim3(grid_for(rows * (kpad - k) * 2, 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad, 2);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(patches_gray_u8_exact_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(patches_gray_u8_exact_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, frames, (uint16_t*)patches, F, R, p, kpad, wrap_quirk);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return launch_patches<PATCH_EXACT_U8, 1>(frames, patches, F, R, p, kpad, wrap_quirk, dtype16, stream);
 }
-
+// Frames that are already normalised floats (HF `pixel_values`, the argument of CLIPModel.get_image_features at
+// extract_embeddings.py:94).
+extern "C" int vmc_patches_f32(const float* pixel_values, void* patches, int F, int R, int p, int kpad, int dtype16, void* stream) {
+  return launch_patches<PATCH_RAW_F32, 3>(pixel_values, patches, F, R, p, kpad, 0, dtype16, stream);
+}
 extern "C" int vmc_patches_f32_split(const float* pixel_values, void* patches, int F, int R, int p, int kpad, int dtype16, void* stream) {
-  if (!pixel_values || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
-  if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
-  if ((uintptr_t)pixel_values & 15) return VMC_E_ALIGN;
-  const size_t total = (size_t)F * 3 * R * (R / 4);
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p);
-    hipLaunchKernelGGL(zero_pad_cols_multi_kernel, dim3(grid_for(rows * (kpad - k) * 3, 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad, 3);
-    VMC_CHECK_LAUNCH();
-  }
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(patches_f32_split_kernel<BF16>, dim3(grid_for(total, 256)), dim3(256), 0, s, pixel_values, (uint16_t*)patches, F, R, p, kpad);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(patches_f32_split_kernel<F16>, dim3(grid_for(total, 256)), dim3(256), 0, s, pixel_values, (uint16_t*)patches, F, R, p, kpad);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return launch_patches<PATCH_SPLIT_F32, 3>(pixel_values, patches, F, R, p, kpad, 0, dtype16, stream);
 }
 
 // ---- Pillow-exact antialiased resample of planar u8 images along one axis (K0) --------------

@@ -216,70 +216,53 @@ def attention(q, k, v, key_mask_u8, B, H, Tq, Tk, dh, want_lse=False, dropout_p=
     return out, lse
 
 
-def preprocess_patches_u8(frames_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
-    F, C, R, R2 = frames_u8.shape
-    if C != 3 or R != R2 or frames_u8.dtype != torch.uint8:
-        raise ValueError("frames must be u8 [F,3,R,R]")
-    frames_u8 = frames_u8.contiguous()
+# vmc_<entry>: (source channels, kpad-wide parts of a patch row, u8 source with a wrap_quirk argument)
+_PATCH_ENTRIES = {"preprocess_patches_u8": (3, 1, True), "preprocess_patches_gray_u8": (1, 1, True),
+                  "patches_u8_exact": (3, 2, True), "patches_gray_u8_exact": (1, 2, True),
+                  "patches_f32": (3, 1, False), "patches_f32_split": (3, 3, False)}
+
+
+def _patches(entry: str, x: torch.Tensor, patch: int, dtype16, wrap_quirk: bool = False) -> torch.Tensor:
+    """x [F,C,R,R] -> the 16-bit patch matrix [F*g*g, parts*kpad] of lib.vmc_<entry> (include/vmc.h), g = R // patch."""
+    channels, parts, u8 = _PATCH_ENTRIES[entry]
+    F, C, R, R2 = x.shape
+    if C != channels or R != R2 or (u8 and x.dtype != torch.uint8):
+        raise ValueError(f"frames must be u8 [F,{channels},R,R]" if u8 else "pixel_values must be [F,3,R,R]")
+    x = (x if u8 else x.float()).contiguous()
     g = R // patch
     kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, kpad), dtype=dtype16, device=frames_u8.device)
-    check(lib.vmc_preprocess_patches_u8(ptr(frames_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()),
-          "preprocess_patches_u8")
+    out = torch.empty((F * g * g, parts * kpad), dtype=dtype16, device=x.device)
+    wrap = (int(wrap_quirk),) if u8 else ()
+    check(getattr(lib, "vmc_" + entry)(ptr(x), ptr(out), F, R, patch, kpad, *wrap, dt(dtype16), stream()), entry)
     return out
+
+
+def preprocess_patches_u8(frames_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
+    return _patches("preprocess_patches_u8", frames_u8, patch, dtype16, wrap_quirk)
 
 
 def patches_f32(pixel_values: torch.Tensor, patch: int, dtype16) -> torch.Tensor:
-    F, C, R, R2 = pixel_values.shape
-    if C != 3 or R != R2:
-        raise ValueError("pixel_values must be [F,3,R,R]")
-    pixel_values = pixel_values.float().contiguous()
-    g = R // patch
-    kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, kpad), dtype=dtype16, device=pixel_values.device)
-    check(lib.vmc_patches_f32(ptr(pixel_values), ptr(out), F, R, patch, kpad, dt(dtype16), stream()), "patches_f32")
-    return out
+    return _patches("patches_f32", pixel_values, patch, dtype16)
 
 
 def patches_u8_exact(frames_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
     """[F*g*g, 2*kpad] = [v | v]: raw pixels as exact 16-bit integers (vmc_patches_u8_exact)."""
-    F, C, R, R2 = frames_u8.shape
-    if C != 3 or R != R2 or frames_u8.dtype != torch.uint8:
-        raise ValueError("frames must be u8 [F,3,R,R]")
-    frames_u8 = frames_u8.contiguous()
-    g = R // patch
-    kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, 2 * kpad), dtype=dtype16, device=frames_u8.device)
-    check(lib.vmc_patches_u8_exact(ptr(frames_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()), "patches_u8_exact")
-    return out
+    return _patches("patches_u8_exact", frames_u8, patch, dtype16, wrap_quirk)
+
+
+def patches_f32_split(pixel_values: torch.Tensor, patch: int, dtype16) -> torch.Tensor:
+    """[F*g*g, 3*kpad] = [x_hi | x_lo | x_hi] (vmc_patches_f32_split)."""
+    return _patches("patches_f32_split", pixel_values, patch, dtype16)
 
 
 def preprocess_patches_gray_u8(gray_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
     """preprocess_patches_u8 of the plane given three times, read once (vmc_preprocess_patches_gray_u8).  gray_u8: u8 [F,1,R,R]."""
-    F, C, R, R2 = gray_u8.shape
-    if C != 1 or R != R2 or gray_u8.dtype != torch.uint8:
-        raise ValueError("frames must be u8 [F,1,R,R]")
-    gray_u8 = gray_u8.contiguous()
-    g = R // patch
-    kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, kpad), dtype=dtype16, device=gray_u8.device)
-    check(lib.vmc_preprocess_patches_gray_u8(ptr(gray_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()),
-          "preprocess_patches_gray_u8")
-    return out
+    return _patches("preprocess_patches_gray_u8", gray_u8, patch, dtype16, wrap_quirk)
 
 
 def patches_gray_u8_exact(gray_u8: torch.Tensor, patch: int, dtype16, wrap_quirk: bool) -> torch.Tensor:
     """patches_u8_exact of the plane given three times, read once (vmc_patches_gray_u8_exact).  gray_u8: u8 [F,1,R,R]."""
-    F, C, R, R2 = gray_u8.shape
-    if C != 1 or R != R2 or gray_u8.dtype != torch.uint8:
-        raise ValueError("frames must be u8 [F,1,R,R]")
-    gray_u8 = gray_u8.contiguous()
-    g = R // patch
-    kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, 2 * kpad), dtype=dtype16, device=gray_u8.device)
-    check(lib.vmc_patches_gray_u8_exact(ptr(gray_u8), ptr(out), F, R, patch, kpad, int(wrap_quirk), dt(dtype16), stream()),
-          "patches_gray_u8_exact")
-    return out
+    return _patches("patches_gray_u8_exact", gray_u8, patch, dtype16, wrap_quirk)
 
 
 GRAY_WEIGHTS_CV8 = (9798, 19235, 3735, 15)      # OpenCV 4.x 8-bit COLOR_BGR2GRAY: R, G, B weights and the shift
@@ -385,19 +368,6 @@ def unit_f32_to_u8(x: torch.Tensor) -> torch.Tensor:
     src = ptr(x)
     if x.numel():
         check(lib.vmc_unit_f32_to_u8(src, ptr(out), x.numel(), stream()), "unit_f32_to_u8")
-    return out
-
-
-def patches_f32_split(pixel_values: torch.Tensor, patch: int, dtype16) -> torch.Tensor:
-    """[F*g*g, 3*kpad] = [x_hi | x_lo | x_hi] (vmc_patches_f32_split)."""
-    F, C, R, R2 = pixel_values.shape
-    if C != 3 or R != R2:
-        raise ValueError("pixel_values must be [F,3,R,R]")
-    pixel_values = pixel_values.float().contiguous()
-    g = R // patch
-    kpad = _kpad(3 * patch * patch)
-    out = torch.empty((F * g * g, 3 * kpad), dtype=dtype16, device=pixel_values.device)
-    check(lib.vmc_patches_f32_split(ptr(pixel_values), ptr(out), F, R, patch, kpad, dt(dtype16), stream()), "patches_f32_split")
     return out
 
 
