@@ -3,7 +3,7 @@
  *
  * The reference (MarcosRodrigoT/VIMO-CLIP) has no FFI: its hot path sits behind Python nn.Module /
  * function signatures and runs on stock PyTorch ATen ops.  Each entry point below replaces the ATen
- * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17..K19 are this project's own).
+ * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17..K20 are this project's own).
  * The Python mirror of the reference interface (vimo_clip_amd/) calls these through ctypes.
  *
  * Conventions
@@ -831,6 +831,23 @@ int vmc_concat_tokens_len(const float* rgb, const float* motion, const uint8_t* 
  * VMC_E_ARG: dx / drgb / dmotion NULL.  VMC_E_SHAPE: as the forward. */
 int vmc_concat_tokens_len_bwd(const float* dx, float* drgb, float* dmotion, int B, int T_rgb, int T_motion, int T_out, int D,
                               const int* len_rgb, const int* len_motion, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K20 — gradient accumulation over micro-batches on the flat gradient arena (optim.GradArena.accumulate).  Every backward
+ * OVERWRITES its slots of the arena; this pass folds what a backward wrote into an fp32 accumulator, so that k micro-batches with
+ * weights B_j / B give the full batch's gradient:
+ *   mode 0  acc[i] = weight * g[i]                   first micro-step: acc needs no zeroing (8 B per element)
+ *   mode 1  acc[i] = fmaf(weight, g[i], acc[i])      (12 B per element)
+ *   mode 2  out[i] = fmaf(weight, g[i], acc[i])      last micro-step; acc is left as it is (12 B per element)
+ * g, acc, out: n fp32 each, 16-BYTE ALIGNED (the kernel moves float4; n itself may be any size, the n % 4 tail is done element by
+ * element).  out may be g itself (the arena finalises in place); any other overlap between the three buffers is not supported.  out
+ * is not touched in modes 0 and 1 (pass g or acc).  The multiply-add is an explicit fmaf -- one rounding, whatever the
+ * compiler's contraction setting -- so with a power-of-two weight the result equals sequential fp32 `acc + weight * g` bit for bit.
+ * inf and NaN propagate.  One launch, plain vector stores, no atomics: the same bits on every call and every replay.  Only
+ * enqueues; safe under capture.
+ * Checked in this order, before any launch: g, acc or out NULL, mode outside 0..2 -> VMC_E_ARG; g, acc or out not
+ * 16-byte aligned -> VMC_E_ALIGN; n == 0 -> success, nothing launched. */
+int vmc_grad_accumulate(const float* g, float* acc, float* out, size_t n, float weight, int mode, void* stream);
 
 #ifdef __cplusplus
 }

@@ -129,6 +129,7 @@ SIGNATURES = {
     "vmc_metric_append": (I, [P, P, P, P, I, P]),
     "vmc_concat_tokens_len": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P]),
     "vmc_concat_tokens_len_bwd": (I, [P, P, P, I, I, I, I, I, P, P, P]),
+    "vmc_grad_accumulate": (I, [P, P, P, Z, F, I, P]),
 }
 
 

@@ -4,7 +4,9 @@
 gradient buffer, Adam m and v): every ``p.data`` / ``p.grad`` becomes a 64-element-aligned view, the
 backward kernels write gradients in place (autograd_ops._grad_out), the optimiser is one vmc_adam_step
 launch over the whole arena (28 B/parameter of HBM traffic), and data-parallel training all-reduces the
-flat gradient buffer in large buckets (parallel.py).  Mirrors ``torch.optim.Adam(lr)`` (train.py:66) and
+flat gradient buffer in large buckets (parallel.py).  Every backward OVERWRITES its gradient slots;
+``GradArena.accumulate`` is the opt-in way to sum the gradients of several micro-batches (vmc_grad_accumulate,
+DESIGN.md "Gradient accumulation").  Mirrors ``torch.optim.Adam(lr)`` (train.py:66) and
 ``torch.optim.AdamW(lr=1e-4, weight_decay=0.1)`` + ``CosineAnnealingLR(T_max=epochs, eta_min=1e-6)``
 (TFAM/train_and_eval.py:53-56) in arithmetic.
 """
@@ -42,11 +44,60 @@ class GradArena:
             g = self.flat_grad[o:o + n].view(p.shape)
             p.grad = g
             p._vmc_grad = g
+        self.flat_acc = None                       # fp32 accumulator of accumulate(), allocated on first use
+        self._pending = 0
+        self._overlap_owner = None                 # the FusedAdam with enable_backward_overlap on, which excludes accumulate()
 
     def zero_grad(self):
-        """Not needed between steps (every used gradient is overwritten by its backward kernel); provided
-        for loops that call it anyway."""
+        """Zero the gradient buffer and DROP a pending accumulation (``pending`` becomes 0; the micro-steps folded so far are
+        forgotten).  Not needed between steps: every used gradient is overwritten, not added to, by its backward kernel, which is
+        also why two backward passes in a row leave the second gradient alone -- summing them takes ``accumulate``."""
         self.flat_grad.zero_()
+        self._pending = 0
+
+    # ---- gradient accumulation over micro-batches ---------------------------------------------------------------------------
+    @property
+    def pending(self) -> int:
+        """Number of micro-steps folded into the accumulator and not yet finalised."""
+        return self._pending
+
+    def _launch_accumulate(self, mode: int, weight: float):
+        check(lib.vmc_grad_accumulate(ptr(self.flat_grad), ptr(self.flat_acc), ptr(self.flat_grad), self.numel, float(weight), mode,
+                                      stream()), "grad_accumulate")
+
+    def accumulate(self, weight: float = 1.0, final: bool = False):
+        """Fold the gradient the last backward wrote into a weighted sum over micro-batches (one streaming launch over the arena).
+
+        Call it after every micro-batch's backward with that micro-batch's weight (rows of the micro-batch / rows of the batch, for
+        losses that are means over rows) and ``final=True`` on the last one: the first call writes ``flat_acc = w * flat_grad``
+        (no zeroing needed), later ones ``flat_acc += w * flat_grad``, the final one ``flat_grad = flat_acc + w * flat_grad`` IN
+        PLACE, so the optimiser, gradient clipping, ``grad_norm`` and the data-parallel reducer read ``flat_grad`` as they always do.
+        ``final=True`` with nothing pending and weight 1 launches nothing (a loop with one micro-batch is the plain, un-accumulated path).
+        ``flat_acc`` costs 4 B per parameter from the first non-final call on.  The pending count lives on the host: the call raises
+        while the current stream is being captured, and it excludes ``FusedAdam.enable_backward_overlap``, which consumes a
+        backward's own gradients."""
+        from . import autograd_ops
+        if self.flat_grad.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("GradArena.accumulate keeps its pending count on the host: it cannot run inside a graph capture")
+        weight = float(weight)
+        if final and not self._pending and weight == 1.0:
+            return
+        if self._overlap_owner is not None:
+            raise RuntimeError("GradArena.accumulate cannot be combined with FusedAdam.enable_backward_overlap: the overlapped "
+                               "optimiser updates parameters from each backward's own gradients (disable_backward_overlap() first)")
+        autograd_ops.wgrad_queue.flush()
+        if self.flat_acc is None:
+            self.flat_acc = torch.empty_like(self.flat_grad)
+        if final:
+            if self._pending:
+                self._launch_accumulate(2, weight)
+            else:                                  # one weighted micro-step on its own: flat_grad = weight * flat_grad (rare; a copy back)
+                self._launch_accumulate(0, weight)
+                self.flat_grad.copy_(self.flat_acc)
+            self._pending = 0
+            return
+        self._launch_accumulate(1 if self._pending else 0, weight)
+        self._pending += 1
 
     def grad_norm(self) -> torch.Tensor:
         from . import autograd_ops
@@ -82,7 +133,9 @@ class FusedAdam:
         self.param_groups = [{"lr": lr}]          # what LR schedulers / loggers poke at
 
     def zero_grad(self, set_to_none: bool = False):
-        pass                                       # gradients are overwritten in place every backward
+        """Does nothing, for loops that call it every step: each backward overwrites its arena slots, so there is nothing to clear
+        (and nothing is ever summed: gradients of several backward passes are combined with ``GradArena.accumulate``).  A pending
+        accumulation is left alone, so calling this before every micro-step is harmless; ``GradArena.zero_grad`` drops it."""
 
     # ---- device-resident step state: what a hipGraph-captured training step needs (ADVICE r1) ----------------------------
     N_SEEDS = 256                                  # dropout call sites per step a model may draw
@@ -168,8 +221,12 @@ class FusedAdam:
         parameter), the backward of the layers below is a chain of latency-bound launches that read none of the updated
         buffers.  ``step()`` afterwards updates whatever is left and joins the side stream.  Same arithmetic, element for
         element, as one whole-arena step.  Only for a single process without gradient clipping (both need the complete
-        gradient first); ``step(grad_scale != 1)`` / ``max_grad_norm`` after a group was already updated raise."""
+        gradient first); ``step(grad_scale != 1)`` / ``max_grad_norm`` after a group was already updated raise.  Excludes
+        ``GradArena.accumulate`` for the same reason: a group would be updated from one micro-batch's gradient."""
         a = self.arena
+        if a.pending:
+            raise RuntimeError("enable_backward_overlap with a pending gradient accumulation: call arena.accumulate(final=True) and "
+                               "step() (or arena.zero_grad()) first")
         index = {id(p): i for i, p in enumerate(a.params)}
         ranges = []
         for g in groups:
@@ -195,10 +252,13 @@ class FusedAdam:
         self._ov = {"ranges": ranges, "rest": rest, "rest_ids": rest_ids, "done": [False] * len(ranges),
                     "stream": torch.cuda.Stream(device=a.flat_param.device, priority=int(os.environ.get("VMC_ADAM_SIDE_PRIO", "0"))),
                     "used": False}
+        a._overlap_owner = self
         return self
 
     def disable_backward_overlap(self):
         self._ov = None
+        if self.arena._overlap_owner is self:
+            self.arena._overlap_owner = None
 
     def _open_step(self):
         if not getattr(self, "_step_open", False):
@@ -241,6 +301,10 @@ class FusedAdam:
         from . import autograd_ops
         autograd_ops.wgrad_queue.flush()               # normally empty: the backward pass flushes its grouped weight gradients itself
         a = self.arena
+        if a.pending:
+            raise RuntimeError(f"FusedAdam.step with {a.pending} micro-step(s) folded into the accumulator and not finalised: the arena "
+                               "holds only the last micro-batch's gradient.  Call arena.accumulate(weight, final=True) after the last "
+                               "backward (or arena.zero_grad() to drop the accumulation)")
         dev_mode = getattr(self, "dev_state", None) is not None
         ov = getattr(self, "_ov", None)
         if dev_mode:

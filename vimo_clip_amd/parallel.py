@@ -11,6 +11,7 @@ Works with the ``gloo`` backend on CPU tensors too (tests/test_parallel_cpu.py, 
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -56,7 +57,11 @@ class GradientAllReducer:
     overlaps it is complete, i.e. in reverse layer order while earlier layers are still back-propagating.  How many reports
     a parameter gets per backward (a packed ``in_proj`` is written in two row slices) is learned from the first step, which
     runs un-overlapped; parameters that never report (unused in the fusion mode) are flushed by ``all_reduce()``.  Every rank
-    runs the same graph, so the launch order of the collectives is the same on every rank."""
+    runs the same graph, so the launch order of the collectives is the same on every rank.
+
+    Gradient accumulation: run every micro-batch's backward under ``no_sync()`` (the arena holds one micro-batch's gradient there,
+    which must not leave), finalise with ``arena.accumulate(w, final=True)``, then ``all_reduce()``: one un-overlapped exchange per
+    optimiser step instead of one per micro-step."""
 
     EXCHANGES = ("all_reduce", "rs_ag")
 
@@ -77,6 +82,22 @@ class GradientAllReducer:
         self.buckets = [flat_grad[s:min(flat_grad.numel(), s + n)] for s in range(0, flat_grad.numel(), n)]
         self._pending = []
         self._attached = False
+        self._no_sync = False
+
+    @contextlib.contextmanager
+    def no_sync(self):
+        """Backward passes inside this block exchange nothing: ``on_grad_ready`` reports are ignored (no bucket is issued, the learned
+        report counts stay as they are) and ``all_reduce()`` / ``start()`` raise.  Leaving the block re-arms the reducer, so the next
+        backward outside it overlaps as before."""
+        if self._no_sync:
+            raise RuntimeError("GradientAllReducer.no_sync() blocks do not nest")
+        self._no_sync = True
+        try:
+            yield self
+        finally:
+            self._no_sync = False
+            if self._attached and self._expected is not None:
+                self._arm()
 
     # ---- overlap with the backward ------------------------------------------------------------------
     def attach(self, arena, register: bool = True):
@@ -122,7 +143,7 @@ class GradientAllReducer:
 
     def on_grad_ready(self, param):
         k = id(param)
-        if not self._attached or world_size() == 1 or k not in self._pbuckets or self._prefs[k]() is not param:
+        if self._no_sync or not self._attached or world_size() == 1 or k not in self._pbuckets or self._prefs[k]() is not param:
             return
         self._counts[k] = self._counts.get(k, 0) + 1
         if self._expected is None or self._counts[k] != self._expected.get(k, 0):
@@ -143,6 +164,8 @@ class GradientAllReducer:
 
     # ---- after the backward ---------------------------------------------------------------------------
     def start(self):
+        if self._no_sync:
+            raise RuntimeError("GradientAllReducer.all_reduce() inside no_sync(): leave the block (and finalise the accumulation) first")
         if world_size() == 1:
             return
         if not self._attached:
@@ -150,7 +173,8 @@ class GradientAllReducer:
             return
         self._n_early = sum(self._launched)
         if self._expected is None:                  # first step: learn the report counts, reduce everything now
-            self._expected = dict(self._counts)
+            if self._counts:                        # (a backward under no_sync() reported nothing: keep waiting for one that does)
+                self._expected = dict(self._counts)
             self._launched = [False] * len(self.buckets)
         for b in range(len(self.buckets)):          # whatever the backward did not complete (unused parameters, padding)
             if not self._launched[b]:
@@ -170,6 +194,8 @@ class GradientAllReducer:
         self._pending = []
         if self._attached and self._expected is not None:
             self._arm()
+        elif self._attached:                        # nothing learned yet (every backward so far ran under no_sync())
+            self._launched = [False] * len(self.buckets)
         return 1.0 / world_size()
 
     def all_reduce(self) -> float:

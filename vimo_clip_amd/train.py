@@ -4,7 +4,8 @@ evaluate :14-49) with the same argument names, one process per GPU under torchru
 h5lite; decoded ``.npy`` frame stacks when no video decoder is installed); ``--synthetic N`` trains on N synthetic
 segments.  ``--single_label`` is the MammalNet variant (train_frame_diff_mn.py:82,102: CrossEntropy on
 ``labels.argmax(dim=1)``, no gradient clipping); ``--motion_key frame_diff`` the frame-difference twin
-(train_frame_diff.py: batch key ``frame_diff`` instead of ``flow_frames``).
+(train_frame_diff.py: batch key ``frame_diff`` instead of ``flow_frames``).  ``--accum_steps N`` (not in the reference) runs every
+batch as up to N micro-batches whose gradients are summed in the arena (optim.GradArena.accumulate); 1 is the loop as it was.
 """
 from __future__ import annotations
 
@@ -37,6 +38,34 @@ def _frames(batch):
     return batch["flow_frames"] if "flow_frames" in batch else batch["frame_diff"]
 
 
+def split_micro_batches(batch, n):
+    """Split a collated batch along its clips into at most ``n`` micro-batches for gradient accumulation: [(sub_batch, weight)].
+    Chunk sizes are ``torch.chunk``'s (ceil(B / n) clips each, the last one smaller, fewer than n chunks when B does not stretch);
+    tensors are split as views, per-clip lists (``video_id``) are sliced alike, anything else is passed to every chunk.  weight =
+    chunk clips / batch clips: the student's losses are means over rows and no operator couples the clips of a batch, so the
+    weighted sum of the micro-batch gradients is the batch's gradient.  n = 1 returns the batch itself with weight 1."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"split_micro_batches: n must be at least 1, got {n}")
+    if n == 1:
+        return [(batch, 1.0)]
+    B = int(batch["labels"].shape[0])
+    per = -(-B // n)
+    bounds = [(s, min(B, s + per)) for s in range(0, B, per)]
+    out = []
+    for lo, hi in bounds:
+        sub = {}
+        for k, v in batch.items():
+            if torch.is_tensor(v) and v.dim() > 0 and v.shape[0] == B:
+                sub[k] = v[lo:hi]
+            elif isinstance(v, (list, tuple)) and len(v) == B:
+                sub[k] = v[lo:hi]
+            else:
+                sub[k] = v
+        out.append((sub, (hi - lo) / B))
+    return out
+
+
 def _class_loss(logits, labels, class_positive_weight, single_label):
     if single_label:                                   # train_frame_diff_mn.py:102
         return cross_entropy_loss(logits, labels.argmax(dim=1))
@@ -62,6 +91,9 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     """datasets: a (train_set, val_set) pair built by the caller instead of the ones the arguments name; collate: its collate function,
     called with the list of samples (a device-side one is bound to its device by the caller); forward_kwargs: keyword arguments of
     every model call (train_frame_diff_mn.py passes ``unit_u8=True`` with its device-side collate)."""
+    accum = int(getattr(args, "accum_steps", 1))
+    if accum < 1:                                           # before anything touches the device
+        raise ValueError(f"--accum_steps must be at least 1, got {accum}")
     rank, world, local = parallel.init_from_env()
     device = f"cuda:{local}"
     E = embed_dim(args.clip_model_name)
@@ -83,13 +115,36 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     parallel.broadcast_parameters(arena.flat_param)
     optimizer = FusedAdam(arena, lr=args.learning_rate)
     reducer = parallel.GradientAllReducer(arena.flat_grad).attach(arena)     # buckets go out during the backward
+    clip_norm = None if single else args.grad_clip_norm
+
+    def micro_loss(batch):
+        emb, emb_d, logits = model(_frames(batch).to(device), **forward_kwargs)
+        dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
+        return dl + _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
     best = float("inf")
     ckpt_dir = getattr(args, "checkpoint_dir", None)       # reference: checkpoints/<run timestamp> (train.py:69-74)
     for epoch in range(args.epochs):
         model.train()
         t0, nframes = time.time(), 0
+        loss_sum, nsteps = (torch.zeros((), device=device) if accum > 1 else None), 0
         for batch in _batches(train_set, args.batch_size, rank, world, collate):
             frames = _frames(batch)
+            if accum > 1:
+                # every chunk is uploaded, run and back-propagated on its own; only the last one exchanges and steps.  The exchange
+                # is not overlapped with the last backward (it needs the finalised sum): one exchange per optimiser step
+                micro = split_micro_batches(batch, accum)
+                step_loss = torch.zeros((), device=device)
+                for j, (sub, w) in enumerate(micro):
+                    with reducer.no_sync():
+                        loss = micro_loss(sub)
+                        loss.backward()
+                    arena.accumulate(w, final=j == len(micro) - 1)
+                    step_loss += w * loss.detach()
+                optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=clip_norm)
+                loss_sum += step_loss
+                nsteps += 1
+                nframes += frames.shape[0] * frames.shape[1]
+                continue
             emb, emb_d, logits = model(frames.to(device), **forward_kwargs)
             dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
             cl = _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
@@ -106,12 +161,15 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
                 save_state_dict(model, f"{ckpt_dir} - best/student_best.pth")
         best = min(best, vt)
         if rank == 0:
-            print(json.dumps({"epoch": epoch + 1, "val_distill": vd, "val_class": vc, "val_total": vt,
-                              "train_frames_per_s_all_gpus": round(nframes * world / (time.time() - t0), 1)}), flush=True)
+            line = {"epoch": epoch + 1, "val_distill": vd, "val_class": vc, "val_total": vt,
+                    "train_frames_per_s_all_gpus": round(nframes * world / (time.time() - t0), 1)}
+            if accum > 1:                                   # mean over the epoch's steps of the weighted sum of the micro-batch losses
+                line["train_total"] = float(loss_sum) / max(1, nsteps)
+            print(json.dumps(line), flush=True)
     return best
 
 
-if __name__ == "__main__":
+def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(description="Train flow-only student model (MI355X engine)")
     p.add_argument("--synthetic", type=int, default=256)
     p.add_argument("--clip_model_name", default="ViT-B/32")
@@ -128,9 +186,16 @@ if __name__ == "__main__":
                                                            "(the reference uses checkpoints/<timestamp>); omitted = no files")
     p.add_argument("--recompute", default="none", choices=["none", "block"],
                    help="block: keep one residual stream per transformer block and recompute the block in the backward pass")
+    p.add_argument("--accum_steps", type=int, default=1,
+                   help="gradient accumulation: split every batch along its clips into at most N micro-batches that are run and "
+                        "back-propagated one after the other; one gradient exchange and one optimiser step per batch")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)
     p.add_argument("--val_clip_embeddings_dir", default=None)
     p.add_argument("--val_flow_videos_dir", default=None)
-    train(p.parse_args())
+    return p
+
+
+if __name__ == "__main__":
+    train(build_parser().parse_args())

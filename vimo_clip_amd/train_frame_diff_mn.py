@@ -35,6 +35,8 @@ def build_parser() -> argparse.ArgumentParser:
     arg("checkpoint_dir", default=None)
     arg("recompute", default="none", choices=["none", "block"],
         help="block: keep one residual stream per transformer block and recompute the block in the backward pass")
+    arg("accum_steps", type=int, default=1,
+        help="gradient accumulation: split every batch along its clips into at most N micro-batches (train.split_micro_batches)")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
