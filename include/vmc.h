@@ -696,7 +696,7 @@ int vmc_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
  * the dropout seeds must not be host scalars frozen into the graph -- ADVICE r1).
  *   state  u64 [2 + n_seeds] in device memory: [0] step count t (start at 0), [1] base seed, [2..] this step's dropout seeds
  *   hyper  f32 [4], 16-byte aligned: {lr, lr / (1 - beta1^t), 1 / sqrt(1 - beta2^t), grad_scale}; the host writes [0] and [3]
- *          (with gradient clipping vmc_grad_clip_dev writes [3], below)
+ *          (with gradient clipping vmc_grad_clip_dev writes [3], with loss scaling vmc_loss_scale_check does: both below)
  * vmc_train_tick: t += 1, recomputes hyper[1..2] and the n_seeds seeds (splitmix of base seed, t and the index); enqueue it once
  * per step before the forward.  vmc_adam_step_dev = vmc_adam_step reading its four scalars from `hyper`.
  * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd): a value < 2^63 is the seed itself; with bit
@@ -716,6 +716,12 @@ int vmc_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, co
  * stream BESIDE other kernels (FusedAdam.enable_backward_overlap: 2 per CU leaves the wave slots the backward's workgroups need). */
 int vmc_adam_step_dev_bg(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
                          float eps, float weight_decay, int decoupled_wd, int max_workgroups, void* stream);
+/* The same update behind a skip flag: `skip` is a DEVICE pointer to one int32 (4-byte aligned).  When *skip != 0 every workgroup
+ * returns before its first store (one uniform 4-byte load per workgroup): p, m and v keep their bytes.  skip == NULL is
+ * vmc_adam_step_dev_bg, which (like vmc_adam_step_dev) is implemented as this call with NULL.  The flag is the `found_inf` word of
+ * a vmc_loss_scale_state (K21). */
+int vmc_adam_step_dev_skip(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
+                           float eps, float weight_decay, int decoupled_wd, int max_workgroups, const int* skip, void* stream);
 /* AdamW update AND refresh of the 16-bit compute copies in one pass over the masters (what `optimizer.step()` followed by
  * vmc_cast_weights_multi does in two: TFAM/train_and_eval.py:96 in a captured step).  desc / n_desc / total_tiles: the records of
  * vmc_cast_weights_multi, every `w` pointing into the flat parameter arena p_base; g_base / m_base / v_base are the parallel arenas
@@ -725,6 +731,11 @@ int vmc_adam_step_dev_bg(float* p, const float* g, float* m, float* v, size_t n,
 int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
                         float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1, float beta2,
                         float eps, float weight_decay, int decoupled_wd, int dtype16, void* stream);
+/* vmc_adam_cast_multi behind the skip flag of vmc_adam_step_dev_skip: with *skip != 0 both launches return before their first
+ * store, so the masters, m, v AND the 16-bit copies keep their bytes.  NULL = vmc_adam_cast_multi, which is this call with NULL. */
+int vmc_adam_cast_multi_skip(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
+                             float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1,
+                             float beta2, float eps, float weight_decay, int decoupled_wd, int dtype16, const int* skip, void* stream);
 /* Gradient clipping computed on the device (torch.nn.utils.clip_grad_norm_, train.py:105-106, inside a captured step): the global
  * norm of `grad` (n floats, 16-byte aligned) and from it the factor the Adam kernels read from hyper[3].  Enqueue it after the
  * backward (and, under data parallelism, after the gradient exchange) and before vmc_adam_step_dev / vmc_adam_cast_multi.
@@ -848,6 +859,44 @@ int vmc_concat_tokens_len_bwd(const float* dx, float* drgb, float* dmotion, int 
  * Checked in this order, before any launch: g, acc or out NULL, mode outside 0..2 -> VMC_E_ARG; g, acc or out not
  * 16-byte aligned -> VMC_E_ALIGN; n == 0 -> success, nothing launched. */
 int vmc_grad_accumulate(const float* g, float* acc, float* out, size_t n, float weight, int mode, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K21 — dynamic loss scaling on the device (torch.amp.GradScaler for float16 training: optim.FusedAdam.enable_loss_scaling).
+ * The loss is multiplied by S before the backward so that float16 gradients stay in range; this call, enqueued where
+ * vmc_grad_clip_dev would be (after the backward and the gradient exchange, before the `_skip` Adam entries), does what
+ * GradScaler.unscale_ + step + update do, without a host read:
+ *   found     = any element of `grad` (n floats, 16-byte aligned, any n >= 1) is +-inf or NaN.  Tested per element: a finite value
+ *               whose fp32 square overflows is not an overflow.
+ *   found_inf = found                                            the skip flag of vmc_adam_step_dev_skip / vmc_adam_cast_multi_skip
+ *   with clip (the record of vmc_grad_clip_dev; clip[0] is NOT read, base_scale comes from `ls`):
+ *     clip[2] = norm = sqrt(sum g^2) * |base_scale| / S          the norm of the UNSCALED averaged gradient
+ *     clip[3] = coef = min(1, clip[1] / (norm + 1e-6))           on overflow: the non-finite norm and the coefficient it gives
+ *   hyper[3]  = found ? 0 : base_scale / S * coef                coef = 1 without clip: the Adam kernels unscale as they read
+ *   the scale, exactly as torch._amp_update_scale_:
+ *     found:  scale *= backoff_factor; growth_tracker = 0; skipped += 1
+ *     else:   ++growth_tracker; when it equals growth_interval: scale *= growth_factor unless that is not finite; tracker = 0
+ *   found and train_state given (the `state` of vmc_train_tick): state[0] -= 1.  The tick at the start of the step had advanced the
+ *     step count; torch does not count a skipped step.  The next tick therefore recomputes the same bias corrections AND THE SAME
+ *     DROPOUT SEEDS: the step after a skipped one draws the masks the skipped one drew (on another batch, at another scale).
+ * The sum of squares is that of vmc_grad_clip_dev, bit for bit (fp32 squares per thread, doubles across threads, fixed order): with a
+ * power-of-two S and no under / overflow, norm, coef and hyper[3] * S equal what vmc_grad_clip_dev gives on the unscaled gradient.
+ * Two launches, no atomics; one thread makes the plain stores.  One read of 4 B per parameter; with clipping it REPLACES
+ * vmc_grad_clip_dev's pass.  workspace: vmc_loss_scale_workspace_bytes(n), 16-byte aligned.  Only enqueues; safe under capture.
+ * VMC_E_ARG: grad / ls / hyper / workspace NULL, n == 0, workspace too small.  VMC_E_ALIGN: grad, ls, hyper, clip or workspace not
+ * 16-byte aligned, train_state not 8-byte aligned. */
+typedef struct vmc_loss_scale_state {
+  float scale;           /* S: host-written at start, device-written afterwards */
+  float growth_factor;   /* host: multiplier after growth_interval clean steps */
+  float backoff_factor;  /* host: multiplier after an overflow */
+  float base_scale;      /* host: what hyper[3] holds without scaling: 1, or 1 / world */
+  int growth_interval;   /* host: clean steps before growth */
+  int growth_tracker;    /* device: clean steps since the last change */
+  int found_inf;         /* device: 0 or 1 for the last checked step; this word is the skip flag */
+  int skipped;           /* device: total skipped steps */
+} vmc_loss_scale_state;
+size_t vmc_loss_scale_workspace_bytes(size_t n);
+int vmc_loss_scale_check(const float* grad, size_t n, vmc_loss_scale_state* ls, float* hyper, float* clip, void* train_state,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,7 @@ class Config:
         self.grad_clip_norm = None # clip_grad_norm_ threshold of every training step (the student's --grad_clip_norm, train.py:105-106); None: no clipping
         self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
         self.device_metrics = False  # log logits / labels / loss on the device inside the step, read once per epoch (metrics.DeviceMetricLog)
+        self.loss_scale = "off"    # "off" | "dynamic" | a number: loss scaling on the device for float16 gradients (optim.FusedAdam.enable_loss_scaling)
         self.fused_feature_training = False  # the feature concatenation (concat_dim = -1) trains on the fused chains too (AMO_CLIP.fused_feature_training)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
@@ -79,6 +80,8 @@ class Config:
             kw["device_metrics"] = bool(t["device_metrics"])
         if "fused_feature_training" in t:           # optional as well
             kw["fused_feature_training"] = bool(t["fused_feature_training"])
+        if t.get("loss_scale") is not None:         # optional as well: off | dynamic | a number (YAML reads `off` as False)
+            kw["loss_scale"] = "off" if t["loss_scale"] is False else str(t["loss_scale"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -309,6 +312,15 @@ class ModelTrainer:
             else:
                 self._graphed_train = GraphedTrainStep(fwd_bwd, self.optimizer, exchange=self.reducer.all_reduce,
                                                        opt_fn=self._device_state_update, **ragged)
+        from ..train import parse_loss_scale
+        scaling = parse_loss_scale(getattr(config, "loss_scale", "off"))
+        self._loss_scaling = scaling is not None
+        if self._loss_scaling:
+            # the scaler lives in device memory: the eager loops move to device-state mode as well (tick() per step); the loss
+            # that is logged and returned stays the unscaled one, the scale enters at the gradient of the logits
+            if getattr(self.optimizer, "dev_state", None) is None:
+                self.optimizer.enable_device_state(base_seed=config.seed if world == 1 else config.seed * 1000 + rank)
+            self.optimizer.enable_loss_scaling(**scaling)
         if world == 1 and os.environ.get("VMC_ADAM_OVERLAP", "0") == "1":
             # AdamW of a finished layer on a side stream beside the backward of the layers below it.  Bit-identical, but measured
             # SLOWER on MI355X (captured B = 8 step 0.88 -> 0.95-1.01 ms: the fork / join edges of a multi-stream hipGraph cost more
@@ -337,7 +349,7 @@ class ModelTrainer:
         self.optimizer.tick()
         output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len, token_lens=token_lens, concat_len=concat_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)      # criterion(output, labels); loss.backward() (:81-83)
-        output.backward(dlogits)
+        output.backward(self.optimizer.scale_grad(dlogits))                # x S on the device with loss scaling, dlogits itself without
         self._device_state_update()
         if self._train_log is not None:
             self._train_log.append(output.detach(), labels, loss)
@@ -354,7 +366,7 @@ class ModelTrainer:
         self.optimizer.tick()
         output = self.model(rgb, mot, mask_rgb=mr, mask_flow=mf, pool_len=pool_len, token_lens=token_lens, concat_len=concat_len)
         loss, dlogits = loss_and_grad(self.criterion, output, labels)
-        output.backward(dlogits)
+        output.backward(self.optimizer.scale_grad(dlogits))
         if self._train_log is not None:
             self._train_log.append(output.detach(), labels, loss)
         return loss, output.detach()
@@ -430,9 +442,11 @@ class ModelTrainer:
                 loss, output = loss.clone(), output.clone()
             else:
                 batch = store.gather(idx, T_rgb, T_motion)
+                if self._loss_scaling:
+                    self.optimizer.tick()
                 output, labels = self._forward(batch)
                 loss = self.criterion(output, labels)
-                loss.backward()
+                self.optimizer.scale_loss(loss).backward()
                 self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
                 if log is not None:
                     log.append(output, labels, loss)
@@ -453,7 +467,7 @@ class ModelTrainer:
         total, n = torch.zeros((), device=self.config.device), 0
         g = torch.Generator().manual_seed(self.config.seed + epoch)
         order = torch.randperm(len(self.train_set), generator=g).tolist()
-        if self._graphed_train is not None:
+        if self._graphed_train is not None or self._loss_scaling:
             self.optimizer.sync_hyper()                     # the epoch's learning rate -> device memory
         log = self._train_log
         if log is not None:
@@ -474,9 +488,11 @@ class ModelTrainer:
                     continue                                            # the step logged itself
                 loss, output = loss.clone(), output.clone()
             else:
+                if self._loss_scaling:
+                    self.optimizer.tick()
                 output, labels = self._forward(batch)
                 loss = self.criterion(output, labels)
-                loss.backward()
+                self.optimizer.scale_loss(loss).backward()       # scaling off: loss itself; logged below: the unscaled loss
                 self.optimizer.step(grad_scale=self.reducer.all_reduce(), max_grad_norm=self.grad_clip_norm)
                 if log is not None:
                     log.append(output, labels, loss)
@@ -541,8 +557,12 @@ class ModelTrainer:
             self.save_checkpoint(vl, vm, epoch)          # best_model.pth when the mAP improved (:157-160)
             self.scheduler.step()
             if self.rank == 0:
-                print(json.dumps({"epoch": epoch + 1, "train_loss": tl, "train_mAP": tm, "val_loss": vl, "val_mAP": vm,
-                                  "lr": self.scheduler.get_last_lr()[0], "elapsed_s": round(time.time() - t0, 1)}), flush=True)
+                line = {"epoch": epoch + 1, "train_loss": tl, "train_mAP": tm, "val_loss": vl, "val_mAP": vm,
+                        "lr": self.scheduler.get_last_lr()[0], "elapsed_s": round(time.time() - t0, 1)}
+                if self._loss_scaling:                   # one small read; the epoch's statistics have synchronised already
+                    rec = self.optimizer.dev_ls.cpu()
+                    line["loss_scale"], line["skipped_steps"] = float(rec.view(torch.float32)[0]), int(rec[7])
+                print(json.dumps(line), flush=True)
         return self.best_val_mAP
 
 
@@ -671,6 +691,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
                     help="with use_graphs and graph_bucket > 1: bucket the two concatenation modes as well")
     ap.add_argument("--fused-feature-training", action="store_true",
                     help="feature concatenation (concat_dim = -1): train on the fused chains, projection layer included")
+    ap.add_argument("--loss-scale", default=None, metavar="{off,dynamic,<number>}",
+                    help="loss scaling on the device for float16 gradients: dynamic, or a number for a static scale (training.loss_scale)")
     ap.add_argument("--device-metrics", action="store_true", help="log loss and metric inputs on the device inside the step, read once per epoch")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
@@ -685,6 +707,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
         over["graph_bucket_concat"] = True
     if args.fused_feature_training:
         over["fused_feature_training"] = True
+    if args.loss_scale is not None:
+        over["loss_scale"] = args.loss_scale
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

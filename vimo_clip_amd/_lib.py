@@ -122,6 +122,8 @@ SIGNATURES = {
     "vmc_adam_step_dev": (I, [P, P, P, P, Z, P, F, F, F, F, I, P]),
     "vmc_adam_step_dev_bg": (I, [P, P, P, P, Z, P, F, F, F, F, I, I, P]),
     "vmc_adam_cast_multi": (I, [P, I, I, P, I, I, P, P, P, P, P, F, F, F, F, I, I, P]),
+    "vmc_adam_step_dev_skip": (I, [P, P, P, P, Z, P, F, F, F, F, I, I, P, P]),
+    "vmc_adam_cast_multi_skip": (I, [P, I, I, P, I, I, P, P, P, P, P, F, F, F, F, I, I, P, P]),
     "vmc_grad_clip_workspace_bytes": (Z, [Z]),
     "vmc_grad_clip_dev": (I, [P, Z, P, P, P, Z, P]),
     "vmc_sumsq": (I, [P, Z, P, P]),
@@ -130,6 +132,8 @@ SIGNATURES = {
     "vmc_concat_tokens_len": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P, P, P]),
     "vmc_concat_tokens_len_bwd": (I, [P, P, P, I, I, I, I, I, P, P, P]),
     "vmc_grad_accumulate": (I, [P, P, P, Z, F, I, P]),
+    "vmc_loss_scale_workspace_bytes": (Z, [Z]),
+    "vmc_loss_scale_check": (I, [P, Z, P, P, P, P, P, Z, P]),
 }
 
 

@@ -358,8 +358,9 @@ template <typename T>
 __global__ void __launch_bounds__(256) adam_cast_multi_kernel(const CastDesc* __restrict__ desc, int n, const float* p_base,
                                                               const float* __restrict__ g_base, float* __restrict__ m_base,
                                                               float* __restrict__ v_base, const float* __restrict__ hyper, float b1, float b2,
-                                                              float eps, float wd, int decoupled) {
+                                                              float eps, float wd, int decoupled, const int* __restrict__ skip) {
   __shared__ uint16_t tile[64][68];
+  if (skip != nullptr && *skip != 0) return;      // a skipped step: masters, moments and 16-bit copies keep their bytes
   const float lr = hyper[0], step_size = hyper[1], inv_sqrt_bc2 = hyper[2], gscale = hyper[3];
   int lo = 0, hi = n - 1;
   while (lo < hi) {
@@ -448,7 +449,8 @@ static_assert(sizeof(AdamRange) == 16, "vmc_adam_cast_multi range layout (includ
 __global__ void __launch_bounds__(256) adam_ranges_kernel(const AdamRange* __restrict__ rr, int n, float* __restrict__ p_base,
                                                           const float* __restrict__ g_base, float* __restrict__ m_base,
                                                           float* __restrict__ v_base, const float* __restrict__ hyper, float b1, float b2, float eps,
-                                                          float wd, int decoupled) {
+                                                          float wd, int decoupled, const int* __restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;
   const float lr = hyper[0], step_size = hyper[1], inv_sqrt_bc2 = hyper[2], gscale = hyper[3];
   int lo = 0, hi = n - 1;
   while (lo < hi) {
@@ -469,28 +471,36 @@ __global__ void __launch_bounds__(256) adam_ranges_kernel(const AdamRange* __res
   }
 }
 
-extern "C" int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
+extern "C" int vmc_adam_cast_multi_skip(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
                                    float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1,
-                                   float beta2, float eps, float weight_decay, int decoupled_wd, int dtype16, void* stream) {
+                                   float beta2, float eps, float weight_decay, int decoupled_wd, int dtype16, const int* skip, void* stream) {
   if (!p_base || !g_base || !m_base || !v_base || !hyper) return VMC_E_ARG;
   if ((n_desc > 0) != (desc != nullptr && total_tiles > 0) || (n_ranges > 0) != (ranges != nullptr && total_range_blocks > 0)) return VMC_E_ARG;
   if (((uintptr_t)p_base | (uintptr_t)g_base | (uintptr_t)m_base | (uintptr_t)v_base | (uintptr_t)hyper) & 15) return VMC_E_ALIGN;
+  if ((uintptr_t)skip & 3) return VMC_E_ALIGN;
   if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
   if (n_desc > 0) {
     if (dtype16 == VMC_BF16)
       hipLaunchKernelGGL(adam_cast_multi_kernel<BF16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc, p_base,
-                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd);
+                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
     else
       hipLaunchKernelGGL(adam_cast_multi_kernel<F16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc, p_base,
-                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd);
+                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
     VMC_CHECK_LAUNCH();
   }
   if (n_ranges > 0) {
     hipLaunchKernelGGL(adam_ranges_kernel, dim3(total_range_blocks), dim3(256), 0, (hipStream_t)stream, (const AdamRange*)ranges, n_ranges, p_base,
-                       g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd);
+                       g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
     VMC_CHECK_LAUNCH();
   }
   return 0;
+}
+
+extern "C" int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
+                                   float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1,
+                                   float beta2, float eps, float weight_decay, int decoupled_wd, int dtype16, void* stream) {
+  return vmc_adam_cast_multi_skip(desc, n_desc, total_tiles, ranges, n_ranges, total_range_blocks, p_base, g_base, m_base, v_base, hyper, beta1,
+                                  beta2, eps, weight_decay, decoupled_wd, dtype16, nullptr, stream);
 }
 
 extern "C" int vmc_cast_weights_multi(const void* desc, int n_desc, int total_tiles, int dtype16, void* stream) {

@@ -1,5 +1,6 @@
 // Losses (value + gradient in one pass) and the fused Adam/AdamW update (gfx950, fp32, HBM-bound).
 #include "common.h"
+#include "grad_sumsq.h"
 
 // ---- distillation loss (losses.py:5-44) ---------------------------------------------------------
 // One wave per row.  Cosine: ns = max(|s|, eps), nt = max(|t|, eps), c = clamp(s.t/(ns nt), +-(1-eps)),
@@ -187,7 +188,8 @@ extern "C" int vmc_cross_entropy_loss(const float* logits, const long long* targ
 __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                    float wd, int decoupled, float step_size, float inv_sqrt_bc2, float gscale,
-                                                   const float* __restrict__ hyper) {
+                                                   const float* __restrict__ hyper, const int* __restrict__ skip) {
+  if (skip != nullptr && *skip != 0) return;      // a skipped step (vmc_loss_scale_check found inf / NaN): uniform, before any store
   if (hyper != nullptr) {      // captured training step: {lr, lr / (1 - b1^t), 1 / sqrt(1 - b2^t), grad_scale} live in device memory
     lr = hyper[0]; step_size = hyper[1]; inv_sqrt_bc2 = hyper[2]; gscale = hyper[3];
   }
@@ -228,7 +230,7 @@ extern "C" int vmc_adam_step(float* p, const float* g, float* m, float* v, size_
   const float step_size = (float)((double)lr / bc1);
   const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for((n + 3) / 4, 256, 256 * 8)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                     beta2, eps, weight_decay, decoupled_wd, step_size, inv_sqrt_bc2, grad_scale, (const float*)nullptr);
+                     beta2, eps, weight_decay, decoupled_wd, step_size, inv_sqrt_bc2, grad_scale, (const float*)nullptr, (const int*)nullptr);
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -266,55 +268,30 @@ extern "C" int vmc_train_tick(void* state, float* hyper, float beta1, float beta
 
 extern "C" int vmc_adam_step_dev(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
                                  float eps, float weight_decay, int decoupled_wd, void* stream) {
-  return vmc_adam_step_dev_bg(p, g, m, v, n, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, 256 * 8, stream);
+  return vmc_adam_step_dev_skip(p, g, m, v, n, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, 256 * 8, nullptr, stream);
 }
 extern "C" int vmc_adam_step_dev_bg(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
                                     float eps, float weight_decay, int decoupled_wd, int max_workgroups, void* stream) {
+  return vmc_adam_step_dev_skip(p, g, m, v, n, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, max_workgroups, nullptr, stream);
+}
+extern "C" int vmc_adam_step_dev_skip(float* p, const float* g, float* m, float* v, size_t n, const float* hyper, float beta1, float beta2,
+                                      float eps, float weight_decay, int decoupled_wd, int max_workgroups, const int* skip, void* stream) {
   if (!p || !g || !m || !v || !hyper || n == 0 || max_workgroups <= 0) return VMC_E_ARG;
   if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)hyper) & 15) return VMC_E_ALIGN;
+  if ((uintptr_t)skip & 3) return VMC_E_ALIGN;
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for((n + 3) / 4, 256, max_workgroups)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.f, beta1,
-                     beta2, eps, weight_decay, decoupled_wd, 0.f, 0.f, 0.f, hyper);
+                     beta2, eps, weight_decay, decoupled_wd, 0.f, 0.f, 0.f, hyper, skip);
   VMC_CHECK_LAUNCH();
   return 0;
 }
 
 // ---- gradient clipping on the device (clip_grad_norm_ inside a captured step, train.py:105-106) -----------------------
-// Store and sum: every workgroup of pass one leaves the sum of squares of its grid-stride share in part[blockIdx.x]; pass two (one
-// workgroup) adds the partials in a fixed order and writes clip[2..3] and hyper[3] (include/vmc.h).  No atomics: the result does not
-// depend on the order in which workgroups finish, so a replayed step repeats bit for bit.  A thread squares and adds in fp32 (at
-// most a few dozen terms per accumulator even for a 33 M-element arena); everything that is summed across threads is a double.
-#define CLIP_BLOCKS 2048      // 256 CUs x 8 workgroups of 256 threads
-__device__ inline double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ inline double block_sum_f64(double a, double* sm) {      // 256 threads, sm = 4 doubles of LDS, one call per kernel
-  a = wave_sum_f64(a);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
-  __syncthreads();
-  return (sm[0] + sm[1]) + (sm[2] + sm[3]);
-}
-
+// Store and sum (grad_sumsq.h, shared with vmc_loss_scale_check): pass one leaves one double per workgroup, pass two (one workgroup)
+// adds them in a fixed order and writes clip[2..3] and hyper[3] (include/vmc.h).
 __global__ void __launch_bounds__(256) grad_sumsq_partial_kernel(const float* __restrict__ g, size_t n, double* __restrict__ part) {
   __shared__ double sm[4];
-  const size_t n4 = n >> 2;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  float4 acc[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
-  // two float4 in flight per thread, as adam_kernel reads them
-  for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
-    const size_t i1 = i0 + stride;
-    const float4 a = ((const float4*)g)[i0];
-    const float4 b = i1 < n4 ? ((const float4*)g)[i1] : make_float4(0.f, 0.f, 0.f, 0.f);
-    acc[0].x += a.x * a.x; acc[0].y += a.y * a.y; acc[0].z += a.z * a.z; acc[0].w += a.w * a.w;
-    acc[1].x += b.x * b.x; acc[1].y += b.y * b.y; acc[1].z += b.z * b.z; acc[1].w += b.w * b.w;
-  }
-  double s = (((double)acc[0].x + (double)acc[0].y) + ((double)acc[0].z + (double)acc[0].w)) +
-             (((double)acc[1].x + (double)acc[1].y) + ((double)acc[1].z + (double)acc[1].w));
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const float t = g[(n4 << 2) + threadIdx.x];
-    s += (double)(t * t);
-  }
+  unsigned bad = 0;
+  double s = grad_sumsq_thread<false>(g, n, bad);
   s = block_sum_f64(s, sm);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
@@ -328,15 +305,12 @@ __global__ void __launch_bounds__(256) grad_clip_finish_kernel(const double* __r
   if (threadIdx.x == 0) {
     const float base = clip[0], max_norm = clip[1];
     const double norm = sqrt(s) * fabs((double)base);                  // of the AVERAGED gradient (optim.clipped_grad_scale)
-    const double c = (double)max_norm / (norm + 1e-6);
-    const float coef = (float)(c < 1.0 ? c : (c != c ? c : 1.0));      // torch.clamp(max=1.0): a NaN norm gives a NaN coefficient
+    const float coef = grad_clip_coef(norm, max_norm);
     clip[2] = (float)norm;
     clip[3] = coef;
     hyper[3] = base * coef;
   }
 }
-
-static inline int grad_clip_blocks(size_t n) { return grid_for(n >> 2, 512, CLIP_BLOCKS); }      // 512 float4 per workgroup and trip
 
 extern "C" size_t vmc_grad_clip_workspace_bytes(size_t n) { return (size_t)grad_clip_blocks(n) * sizeof(double); }
 

@@ -136,7 +136,8 @@ class GraphedTrainStep:
     TWO graphs with the gradient exchange between them -- ``step_fn`` = tick + forward + loss + backward (one graph per batch
     shape), then ``exchange()`` (the bucketed RCCL all-reduce or reduce-scatter + all-gather of parallel.GradientAllReducer, eager:
     collectives are not captured) whose return value (1 / world) goes to the optimiser's device-resident grad_scale, then
-    ``opt_fn`` = [vmc_grad_clip_dev over the rank-summed arena when it passes ``max_grad_norm``, base_scale = 1 / world +] the fused
+    ``opt_fn`` = [vmc_grad_clip_dev over the rank-summed arena when it passes ``max_grad_norm``, base_scale = 1 / world, or with
+    ``FusedAdam.enable_loss_scaling`` vmc_loss_scale_check: every rank sees the same exchanged arena, so all skip together +] the fused
     AdamW + the refresh of the 16-bit copies (one graph, shape independent).  Gradient-ready hooks are
     silenced while capturing (a replay runs no Python, so the buckets go out after the backward graph, not during it).
 
@@ -190,6 +191,8 @@ class GraphedTrainStep:
         live = (a.flat_param, a.flat_grad, o.m, o.v, o.dev_state, o.dev_hyper)
         clip = getattr(o, "dev_clip", None)            # device-side gradient clipping in use: its norm / coefficient slots too
         live = live if clip is None else live + (clip,)
+        ls = getattr(o, "dev_ls", None)                # loss scaling on: a warm-up leaves S, the tracker and the counters as it found them
+        live = live if ls is None else live + (ls,)
         return live + self.extra_live
 
     def _capture(self, fn, inputs):

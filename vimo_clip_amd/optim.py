@@ -12,6 +12,7 @@ DESIGN.md "Gradient accumulation").  Mirrors ``torch.optim.Adam(lr)`` (train.py:
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 
@@ -121,6 +122,29 @@ def clipped_grad_scale(sum_grad_norm: float, grad_scale: float, max_grad_norm: f
     return grad_scale * min(1.0, max_grad_norm / (total + 1e-6))
 
 
+class LossScaleStruct(ctypes.Structure):
+    """ctypes mirror of ``vmc_loss_scale_state`` (include/vmc.h): same fields in the same order, 32 bytes."""
+    _fields_ = [("scale", ctypes.c_float), ("growth_factor", ctypes.c_float), ("backoff_factor", ctypes.c_float),
+                ("base_scale", ctypes.c_float), ("growth_interval", ctypes.c_int), ("growth_tracker", ctypes.c_int),
+                ("found_inf", ctypes.c_int), ("skipped", ctypes.c_int)]
+
+
+class _ScaleLossFn(torch.autograd.Function):
+    """loss * S with S read from device memory by the kernel, forward and backward (vmc_scale_by_device_scalar): nothing of S is a
+    host scalar, so the node is safe under capture and S may change between replays."""
+
+    @staticmethod
+    def forward(ctx, loss, scale):
+        from . import autograd_ops
+        ctx.scale = scale
+        return autograd_ops.scale_by_device_scalar(loss.contiguous().float(), scale)
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import autograd_ops
+        return autograd_ops.scale_by_device_scalar(g.contiguous().float(), ctx.scale), None
+
+
 class FusedAdam:
     """Adam / AdamW over a GradArena: one kernel launch per step."""
 
@@ -151,21 +175,26 @@ class FusedAdam:
         self.dev_state[1] = int(base_seed) & 0x7FFFFFFFFFFFFFFF
         self.dev_hyper = torch.zeros(4, dtype=torch.float32, device=dev)
         self.dev_clip = self._clip_ws = self._clip_max = None
+        self.dev_ls = self._ls_ws = self._ls_f32 = None
         self._hyper_host = None
         self.sync_hyper()
         return self
 
     def sync_hyper(self, grad_scale: float = 1.0):
         """lr and grad_scale (1, or 1 / world over a rank-summed arena) -> device memory, only when one of them changed.  While
-        clipping is on, hyper[3] belongs to vmc_grad_clip_dev: grad_scale goes to dev_clip[0] (base_scale) beside the threshold."""
-        want = (float(self.param_groups[0]["lr"]), float(grad_scale), self._clip_max)
+        clipping is on, hyper[3] belongs to vmc_grad_clip_dev: grad_scale goes to dev_clip[0] (base_scale) beside the threshold.
+        While loss scaling is on, hyper[3] belongs to vmc_loss_scale_check: grad_scale goes to the scaler record's base_scale (and,
+        with clipping, to dev_clip[0] as well)."""
+        want = (float(self.param_groups[0]["lr"]), float(grad_scale), self._clip_max, self.dev_ls is not None)
         if self._hyper_host != want:
             self.dev_hyper[0] = want[0]
-            if self._clip_max is None:
-                self.dev_hyper[3] = want[1]
-            else:
+            if self.dev_ls is not None:
+                self._ls_f32[3] = want[1]
+            if self._clip_max is not None:
                 self.dev_clip[0] = want[1]
                 self.dev_clip[1] = want[2]
+            elif self.dev_ls is None:
+                self.dev_hyper[3] = want[1]
             self._hyper_host = want
 
     def _set_clip(self, max_grad_norm):
@@ -200,6 +229,94 @@ class FusedAdam:
             raise RuntimeError("no device-side clipping yet: enable_device_state() and step(max_grad_norm=...) come first")
         return self.dev_clip[i:i + 1]
 
+    # ---- dynamic loss scaling on the device (float16 training; DESIGN.md "Dynamic loss scaling") ---------------------------
+    def enable_loss_scaling(self, init_scale: float = 65536.0, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                            growth_interval: int = 2000):
+        """torch.amp.GradScaler, on the device.  ``scale_loss(loss).backward()`` (or ``out.backward(scale_grad(dlogits))``) produces
+        gradients multiplied by S; ``step()`` then runs vmc_loss_scale_check where it runs vmc_grad_clip_dev otherwise -- per-element
+        inf / NaN test, the unscaled norm for ``max_grad_norm``, hyper[3] = grad_scale / S * coefficient, the scale update of
+        ``torch._amp_update_scale_`` -- and the Adam entries behind the skip flag: after an overflow parameters, moments and 16-bit
+        copies keep their bytes, S is multiplied by ``backoff_factor`` and the device step count is taken back, so the next ``tick()``
+        recomputes the same bias corrections and dropout seeds.  Nothing is read back: captured and no-sync steps keep their shape.
+        ``growth_factor = backoff_factor = 1`` is a static scale (an overflowing step is still skipped).
+        Needs ``enable_device_state()``; excludes ``enable_backward_overlap`` (parameters updated before the gradient is complete
+        cannot be skipped).  The host's ``step_count`` counts ATTEMPTS from here on; the true count is ``dev_state[0]`` (which
+        ``state_dict()`` reads).  Writes device memory from the host: raises inside a capture."""
+        if getattr(self, "dev_state", None) is None:
+            raise RuntimeError("enable_loss_scaling needs enable_device_state() first: the scaler lives in device memory")
+        if getattr(self, "_ov", None) is not None:
+            raise RuntimeError("enable_loss_scaling cannot be combined with enable_backward_overlap: an overlapped step updates "
+                               "parameters before the gradient is complete, so it cannot be skipped")
+        if not (init_scale > 0.0 and math.isfinite(init_scale)) or growth_factor < 1.0 or not 0.0 < backoff_factor <= 1.0 or growth_interval < 1:
+            raise ValueError("enable_loss_scaling: init_scale > 0, growth_factor >= 1, 0 < backoff_factor <= 1, growth_interval >= 1")
+        dev = self.dev_hyper.device
+        if self.dev_hyper.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("enable_loss_scaling while a graph is being captured: enable it before the first captured step")
+        grad_scale = self._hyper_host[1] if self._hyper_host is not None else 1.0
+        rec = LossScaleStruct(float(init_scale), float(growth_factor), float(backoff_factor), float(grad_scale), int(growth_interval), 0, 0, 0)
+        self.dev_ls = torch.frombuffer(bytearray(bytes(rec)), dtype=torch.int32).clone().to(dev)
+        self._ls_f32 = self.dev_ls.view(torch.float32)
+        if dev.type == "cuda":
+            self._ls_ws = torch.empty(int(lib.vmc_loss_scale_workspace_bytes(self.arena.numel)), dtype=torch.uint8, device=dev)
+        self._hyper_host = None
+        self.sync_hyper(grad_scale)
+        return self
+
+    def disable_loss_scaling(self):
+        """The host owns hyper[3] again (as ``_set_clip(None)``); gradients must be unscaled from the next backward on."""
+        if getattr(self, "dev_ls", None) is None:
+            return
+        if self.dev_hyper.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("disable_loss_scaling while a graph is being captured")
+        grad_scale = self._hyper_host[1] if self._hyper_host is not None else 1.0
+        self.dev_ls = self._ls_ws = self._ls_f32 = None
+        self._hyper_host = None
+        self.sync_hyper(grad_scale)
+
+    @property
+    def loss_scaling(self) -> bool:
+        return getattr(self, "dev_ls", None) is not None
+
+    def _ls_need(self):
+        if not self.loss_scaling:
+            raise RuntimeError("loss scaling is off: enable_device_state() and enable_loss_scaling() come first")
+
+    @property
+    def loss_scale(self):
+        """One-element device view (fp32): the scale S the NEXT backward will use.  No synchronisation."""
+        self._ls_need()
+        return self._ls_f32[0:1]
+
+    @property
+    def last_found_inf(self):
+        """One-element device view (int32): 1 if the last ``step()`` found inf / NaN and was skipped."""
+        self._ls_need()
+        return self.dev_ls[6:7]
+
+    @property
+    def skipped_steps(self):
+        """One-element device view (int32): steps skipped since ``enable_loss_scaling`` (or the loaded checkpoint)."""
+        self._ls_need()
+        return self.dev_ls[7:8]
+
+    def scale_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """``loss * S`` through an autograd node whose backward multiplies by S read from device memory at run time; ``loss`` itself
+        stays the unscaled value for logging.  With scaling off: ``loss`` unchanged."""
+        if not self.loss_scaling:
+            return loss
+        return _ScaleLossFn.apply(loss, self._ls_f32[0:1])
+
+    def scale_grad(self, dlogits: torch.Tensor) -> torch.Tensor:
+        """``dlogits * S`` for the ``loss_and_grad`` / ``output.backward(dlogits)`` pattern (one launch, S read on the device)."""
+        if not self.loss_scaling:
+            return dlogits
+        from . import autograd_ops
+        return autograd_ops.scale_by_device_scalar(dlogits.contiguous().float(), self._ls_f32[0:1]).view(dlogits.shape)
+
+    def _skip_ptr(self):
+        """Address of the scaler record's found_inf word: the skip flag of the Adam entries (None = no flag)."""
+        return None if getattr(self, "dev_ls", None) is None else self.dev_ls.data_ptr() + 24
+
     def tick(self):
         """Start of a step in device-state mode: t += 1, bias corrections and this step's dropout seeds (one launch)."""
         check(lib.vmc_train_tick(ptr(self.dev_state), ptr(self.dev_hyper), float(self.betas[0]), float(self.betas[1]), self.N_SEEDS,
@@ -224,6 +341,9 @@ class FusedAdam:
         gradient first); ``step(grad_scale != 1)`` / ``max_grad_norm`` after a group was already updated raise.  Excludes
         ``GradArena.accumulate`` for the same reason: a group would be updated from one micro-batch's gradient."""
         a = self.arena
+        if getattr(self, "dev_ls", None) is not None:
+            raise RuntimeError("enable_backward_overlap cannot be combined with loss scaling: an overlapped step updates parameters "
+                               "before the gradient is complete, so it cannot be skipped (disable_loss_scaling() first)")
         if a.pending:
             raise RuntimeError("enable_backward_overlap with a pending gradient accumulation: call arena.accumulate(final=True) and "
                                "step() (or arena.zero_grad()) first")
@@ -274,9 +394,9 @@ class FusedAdam:
             return
         p, g, m, v = a.flat_param[lo:hi], a.flat_grad[lo:hi], self.m[lo:hi], self.v[lo:hi]
         if getattr(self, "dev_state", None) is not None:
-            check(lib.vmc_adam_step_dev_bg(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.dev_hyper), float(self.betas[0]), float(self.betas[1]),
-                                           float(self.eps), float(self.weight_decay), int(self.decoupled),
-                                           self.BG_WORKGROUPS if background else 2048, stream()), "adam_step_dev")
+            check(lib.vmc_adam_step_dev_skip(ptr(p), ptr(g), ptr(m), ptr(v), n, ptr(self.dev_hyper), float(self.betas[0]), float(self.betas[1]),
+                                             float(self.eps), float(self.weight_decay), int(self.decoupled),
+                                             self.BG_WORKGROUPS if background else 2048, self._skip_ptr(), stream()), "adam_step_dev")
         else:
             check(lib.vmc_adam_step(ptr(p), ptr(g), ptr(m), ptr(v), n, float(self.param_groups[0]["lr"]), float(self.betas[0]),
                                     float(self.betas[1]), float(self.eps), float(self.weight_decay), int(self.decoupled), self.step_count,
@@ -311,6 +431,8 @@ class FusedAdam:
             if max_grad_norm is not None and ov is not None:
                 raise ValueError("backward-overlapped optimiser steps cannot be combined with grad_scale / max_grad_norm")
             self._set_clip(max_grad_norm)
+            if self.dev_ls is not None and grad_scale != 1.0:      # the reducer's 1 / world -> the scaler record's base_scale (host write,
+                self.sync_hyper(grad_scale)                        # only when it changes: never inside a capture, whose steps pass 1)
         if ov is not None and ov["used"]:
             # some ranges were updated during the backward: finish the others on this stream, then join
             if max_grad_norm is not None or grad_scale != 1.0:
@@ -329,7 +451,11 @@ class FusedAdam:
             ov["used"] = False
             self._step_open = False
             return
-        if max_grad_norm is not None and dev_mode:  # the same, computed on the device: hyper[3] = base_scale * coefficient
+        if dev_mode and self.dev_ls is not None:    # found-inf check, unscaled norm, hyper[3] = base_scale / S * coefficient, scale update
+            check(lib.vmc_loss_scale_check(ptr(a.flat_grad), a.numel, ptr(self.dev_ls), ptr(self.dev_hyper),
+                                           ptr(self.dev_clip) if max_grad_norm is not None else None, ptr(self.dev_state),
+                                           ptr(self._ls_ws), self._ls_ws.numel(), stream()), "loss_scale_check")
+        elif max_grad_norm is not None and dev_mode:  # the same, computed on the device: hyper[3] = base_scale * coefficient
             check(lib.vmc_grad_clip_dev(ptr(a.flat_grad), a.numel, ptr(self.dev_hyper), ptr(self.dev_clip), ptr(self._clip_ws),
                                         self._clip_ws.numel(), stream()), "grad_clip_dev")
         elif max_grad_norm is not None:            # torch.nn.utils.clip_grad_norm_ (train.py:105-106)
@@ -375,14 +501,21 @@ class FusedAdam:
                 block0 += (n + 1023) // 1024
             plan = self._fused_plan = (covered, torch.from_numpy(rec).to(a.flat_param.device), len(rest), block0)
             self._old_plans = getattr(self, "_old_plans", []) + [plan[1]]      # a captured graph may still read an older table
-        check(lib.vmc_adam_cast_multi(ptr(tab[1]), tab[2], tab[3], ptr(plan[1]) if plan[2] else None, plan[2], plan[3], ptr(a.flat_param),
-                                      ptr(a.flat_grad), ptr(self.m), ptr(self.v), ptr(self.dev_hyper), float(self.betas[0]), float(self.betas[1]),
-                                      float(self.eps), float(self.weight_decay), int(self.decoupled), dt(dtype16), stream()), "adam_cast_multi")
+        check(lib.vmc_adam_cast_multi_skip(ptr(tab[1]), tab[2], tab[3], ptr(plan[1]) if plan[2] else None, plan[2], plan[3], ptr(a.flat_param),
+                                           ptr(a.flat_grad), ptr(self.m), ptr(self.v), ptr(self.dev_hyper), float(self.betas[0]),
+                                           float(self.betas[1]), float(self.eps), float(self.weight_decay), int(self.decoupled), dt(dtype16),
+                                           self._skip_ptr(), stream()), "adam_cast_multi")
         autograd_ops.weights.epoch += 1
         return True
 
     def state_dict(self):
-        return {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.param_groups[0]["lr"]}
+        """With loss scaling on, ``step`` is the TRUE step count read from the device (one synchronising read: the host mirror counts
+        attempts, skipped steps included) and ``loss_scale`` carries the scaler record (8 int32 words, vmc_loss_scale_state)."""
+        sd = {"step": self.step_count, "m": self.m, "v": self.v, "lr": self.param_groups[0]["lr"]}
+        if getattr(self, "dev_ls", None) is not None:
+            sd["step"] = int(self.dev_state[0].item())
+            sd["loss_scale"] = self.dev_ls.detach().cpu().clone()
+        return sd
 
     def load_state_dict(self, sd):
         """Layout {step, m, v, lr} over the flat arena (NOT torch.optim's per-parameter state: checkpoint.py says so)."""
@@ -392,6 +525,8 @@ class FusedAdam:
         self.param_groups[0]["lr"] = sd["lr"]
         if getattr(self, "dev_state", None) is not None:      # device-state mode: the step count and lr the kernels read
             self.dev_state[0] = self.step_count
+            if sd.get("loss_scale") is not None and self.dev_ls is not None:      # S, factors, interval, tracker, counters
+                self.dev_ls.copy_(sd["loss_scale"].to(torch.int32))
             self._hyper_host = None
             self.sync_hyper()
 

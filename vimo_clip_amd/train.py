@@ -6,6 +6,8 @@ segments.  ``--single_label`` is the MammalNet variant (train_frame_diff_mn.py:8
 ``labels.argmax(dim=1)``, no gradient clipping); ``--motion_key frame_diff`` the frame-difference twin
 (train_frame_diff.py: batch key ``frame_diff`` instead of ``flow_frames``).  ``--accum_steps N`` (not in the reference) runs every
 batch as up to N micro-batches whose gradients are summed in the arena (optim.GradArena.accumulate); 1 is the loop as it was.
+``--compute_dtype f16`` trains in float16 and ``--loss_scale dynamic|<number>`` (neither in the reference) keeps its gradients in
+range: the optimiser moves to device-state mode and scales, checks and skips on the device (optim.FusedAdam.enable_loss_scaling).
 """
 from __future__ import annotations
 
@@ -66,6 +68,35 @@ def split_micro_batches(batch, n):
     return out
 
 
+COMPUTE_DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16}
+
+
+def parse_loss_scale(text):
+    """``--loss_scale`` -> None ("off"), or the keyword arguments of ``FusedAdam.enable_loss_scaling``: "dynamic" = GradScaler's
+    defaults (2^16, x2 after 2000 clean steps, x0.5 after an overflow); a number = that scale, static (growth = backoff = 1; an
+    overflowing step is still skipped).  Anything else raises ValueError."""
+    text = str(text).strip().lower()
+    if text == "off":
+        return None
+    if text == "dynamic":
+        return {}
+    try:
+        scale = float(text)
+    except ValueError:
+        raise ValueError(f"--loss_scale must be off, dynamic or a positive number, got {text!r}") from None
+    if not (scale > 0.0 and scale < float("inf")):
+        raise ValueError(f"--loss_scale must be off, dynamic or a positive number, got {text!r}")
+    return {"init_scale": scale, "growth_factor": 1.0, "backoff_factor": 1.0}
+
+
+def _loss_scale_arg(text):
+    try:
+        parse_loss_scale(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return str(text).strip().lower()
+
+
 def _class_loss(logits, labels, class_positive_weight, single_label):
     if single_label:                                   # train_frame_diff_mn.py:102
         return cross_entropy_loss(logits, labels.argmax(dim=1))
@@ -109,13 +140,18 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     else:
         train_set = SyntheticSegmentDataset(args.synthetic, args.sequence_length, E, args.num_classes, seed=3)
         val_set = SyntheticSegmentDataset(max(args.batch_size * world, args.synthetic // 8), args.sequence_length, E, args.num_classes, seed=4)
+    dtype_name = getattr(args, "compute_dtype", "bf16")
     model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha,
-                             recompute=getattr(args, "recompute", "none"))
+                             recompute=getattr(args, "recompute", "none"),
+                             **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}))
     arena = GradArena(model.parameters())
     parallel.broadcast_parameters(arena.flat_param)
     optimizer = FusedAdam(arena, lr=args.learning_rate)
     reducer = parallel.GradientAllReducer(arena.flat_grad).attach(arena)     # buckets go out during the backward
     clip_norm = None if single else args.grad_clip_norm
+    scaling = parse_loss_scale(getattr(args, "loss_scale", "off"))
+    if scaling is not None:                                # the scaler lives in device memory: device-state mode, tick() per step
+        optimizer.enable_device_state().enable_loss_scaling(**scaling)
 
     def micro_loss(batch):
         emb, emb_d, logits = model(_frames(batch).to(device), **forward_kwargs)
@@ -129,6 +165,8 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
         loss_sum, nsteps = (torch.zeros((), device=device) if accum > 1 else None), 0
         for batch in _batches(train_set, args.batch_size, rank, world, collate):
             frames = _frames(batch)
+            if scaling is not None:
+                optimizer.tick()
             if accum > 1:
                 # every chunk is uploaded, run and back-propagated on its own; only the last one exchanges and steps.  The exchange
                 # is not overlapped with the last backward (it needs the finalised sum): one exchange per optimiser step
@@ -136,8 +174,8 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
                 step_loss = torch.zeros((), device=device)
                 for j, (sub, w) in enumerate(micro):
                     with reducer.no_sync():
-                        loss = micro_loss(sub)
-                        loss.backward()
+                        loss = micro_loss(sub)                  # the unscaled loss: what is logged
+                        optimizer.scale_loss(loss).backward()   # scaling off: loss itself
                     arena.accumulate(w, final=j == len(micro) - 1)
                     step_loss += w * loss.detach()
                 optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=clip_norm)
@@ -148,7 +186,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
             emb, emb_d, logits = model(frames.to(device), **forward_kwargs)
             dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
             cl = _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
-            (dl + cl).backward()
+            optimizer.scale_loss(dl + cl).backward()
             optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=None if single else args.grad_clip_norm)
             nframes += frames.shape[0] * frames.shape[1]
         torch.cuda.synchronize()
@@ -165,6 +203,9 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
                     "train_frames_per_s_all_gpus": round(nframes * world / (time.time() - t0), 1)}
             if accum > 1:                                   # mean over the epoch's steps of the weighted sum of the micro-batch losses
                 line["train_total"] = float(loss_sum) / max(1, nsteps)
+            if scaling is not None:                         # one small read where the loop has already synchronised
+                rec = optimizer.dev_ls.cpu()
+                line["loss_scale"], line["skipped_steps"] = float(rec.view(torch.float32)[0]), int(rec[7])
             print(json.dumps(line), flush=True)
     return best
 
@@ -189,6 +230,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--accum_steps", type=int, default=1,
                    help="gradient accumulation: split every batch along its clips into at most N micro-batches that are run and "
                         "back-propagated one after the other; one gradient exchange and one optimiser step per batch")
+    p.add_argument("--compute_dtype", default="bf16", choices=list(COMPUTE_DTYPES), help="16-bit type of the GEMM and attention operands")
+    p.add_argument("--loss_scale", default="off", type=_loss_scale_arg, metavar="{off,dynamic,<number>}",
+                   help="loss scaling for float16 gradients, on the device: dynamic = GradScaler's defaults; a number = a static "
+                        "scale; an overflowing step is skipped either way")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

@@ -37,12 +37,16 @@ def build_parser() -> argparse.ArgumentParser:
         help="block: keep one residual stream per transformer block and recompute the block in the backward pass")
     arg("accum_steps", type=int, default=1,
         help="gradient accumulation: split every batch along its clips into at most N micro-batches (train.split_micro_batches)")
+    arg("compute_dtype", default="bf16", choices=["bf16", "f16"], help="16-bit type of the GEMM and attention operands")
+    arg("loss_scale", default="off", metavar="{off,dynamic,<number>}",
+        help="loss scaling for float16 gradients, on the device (train.parse_loss_scale): dynamic, or a number for a static scale")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
 
 def train(args):
     from . import train as student_train
+    student_train.parse_loss_scale(args.loss_scale)         # a malformed value fails before any file is opened
     size = tuple(args.spatial_size)
     sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
                                   raw_u8=args.device_resize) for path in (args.train_hdf5_path, args.val_hdf5_path))
