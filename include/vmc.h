@@ -239,7 +239,9 @@ int vmc_cast_weight(const float* w, void* w16, void* w16_t, int rows, int cols, 
 /* The same for many weights in ONE launch: after an optimiser step (`optimizer.step()`, train.py:107, TFAM/train_and_eval.py:96)
  * every 16-bit compute copy of the trained parameters is refreshed in place.  `desc` is a DEVICE array of n_desc records of
  * 48 bytes {const float* w; void* w16; void* w16_t; int rows, cols, ld_out, ld_out_t, tile0, tiles_x;} (NULL copies are skipped);
- * record i owns the 64x64 tiles [tile0, tile0 of record i+1) of a 1-D grid of total_tiles, tiles_x = ceil(cols / 64). */
+ * record i owns the 64x64 tiles [tile0, tile0 of record i+1) of a 1-D grid of total_tiles, tiles_x = ceil(cols / 64).
+ * 16-byte loads and 8-byte stores where a record's w is 16-byte aligned, its copies 8-byte aligned and rows, cols, ld_out and
+ * ld_out_t are multiples of 4; scalar accesses for a record where they are not (neither is an error). */
 int vmc_cast_weights_multi(const void* desc, int n_desc, int total_tiles, int dtype16, void* stream);
 
 /* Column sums  out[n] = sum_m in[m, n]  (bias gradients, K8).  N % 4 == 0, ld_in % 4 == 0.  workspace: >= vmc_colsum_workspace_bytes. */
@@ -727,7 +729,9 @@ int vmc_adam_step_dev_skip(float* p, const float* g, float* m, float* v, size_t 
  * vmc_cast_weights_multi, every `w` pointing into the flat parameter arena p_base; g_base / m_base / v_base are the parallel arenas
  * (element i of a tensor at the same offset in all four).  ranges: DEVICE array of n_ranges records of 16 bytes
  * {uint64 offset; int32 n; int32 block0} for the arena slices that have no compute copy (biases, LayerNorm parameters, ...), record i
- * owning blocks [block0, block0 of i+1) of 1024 elements.  Same arithmetic as vmc_adam_step_dev, bit for bit. */
+ * owning blocks [block0, block0 of i+1) of 1024 elements.  Same arithmetic as vmc_adam_step_dev, bit for bit.  The four bases are
+ * 16-byte aligned (VMC_E_ALIGN); a record whose w is not, or whose shape or strides are not multiples of 4, is handled with scalar
+ * accesses to the arenas and the copies, as in vmc_cast_weights_multi (not an error). */
 int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles, const void* ranges, int n_ranges, int total_range_blocks,
                         float* p_base, const float* g_base, float* m_base, float* v_base, const float* hyper, float beta1, float beta2,
                         float eps, float weight_decay, int decoupled_wd, int dtype16, void* stream);

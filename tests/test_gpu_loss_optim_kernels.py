@@ -23,7 +23,7 @@ DEV = "cuda"
 F32, F64, BF16, F16 = R.F32, R.F64, R.BF16, R.F16
 DT16 = [BF16, F16]
 DT16_IDS = ["bf16", "f16"]
-E_ARG, E_ALIGN = -1, -2
+E_ARG, E_ALIGN, E_DTYPE = -1, -2, -4
 NAN = float("nan")
 SENTINEL = 12345.0
 LR, B1, B2, EPS = R.ADAM_LR, R.ADAM_B1, R.ADAM_B2, R.ADAM_EPS
@@ -457,6 +457,7 @@ def test_colsum_error_codes():
     assert call("vmc_colsum", p(x), p(out), 4, 8, 10, L.F32, p(ws), 256, L.stream()) == E_ALIGN      # ld_in % 4
     assert call("vmc_colsum", p(x), p(out), 4, 8, 4, L.F32, p(ws), 256, L.stream()) == E_ARG         # ld_in < N
     assert call("vmc_colsum", p(x), p(out), 4, 8, 8, L.F32, p(ws), 8 * 4 - 1, L.stream()) == E_ARG   # short workspace
+    assert call("vmc_colsum", p(x), p(out), 4, 8, 8, 7, p(ws), 8 * 4, L.stream()) == E_DTYPE         # in_dtype not f32 / bf16 / f16
     assert call("vmc_colsum", p(x), p(out), 4, 8, 8, L.F32, p(ws), 8 * 4, L.stream()) == 0
     sync()
 
@@ -485,10 +486,11 @@ def test_transpose16(rows, cols, dt16):
 
 
 @pytest.mark.parametrize("dt16", DT16, ids=DT16_IDS)
-@pytest.mark.parametrize("rows,cols", R.T16_SHAPES)
+@pytest.mark.parametrize("rows,cols", R.T16_SHAPES + ((68, 132),))
 def test_cast_weight(rows, cols, dt16):
     """vmc_cast_weight: the plain copy, the copy padded to a multiple of 64 columns, the transposed (padded) copy alone and both in one
-    launch -- bit-equal to the CPU cast (ties, overflow, subnormals, infinities planted; any NaN matches any NaN), pad columns exactly 0."""
+    launch -- bit-equal to the CPU cast (ties, overflow, subnormals, infinities planted; any NaN matches any NaN), pad columns exactly 0.
+    64 x 64 and 68 x 132 (six tiles, ragged edges both ways) take the 4-wide path, the other shapes the scalar one."""
     w = TR.cast_inputs_f32(rows * cols, dt16).view(rows, cols).contiguous()
     ref = w.to(dt16)
     w_d = dev(w)

@@ -263,6 +263,52 @@ def test_adam_cast_multi_skip(dtype):
     ag.weights.clear()
 
 
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "f16"])
+def test_adam_cast_multi_master_at_an_odd_float(dtype):
+    """A hand-built table of one record: a 68 x 132 master at p_base + 1 float, so 4-byte aligned only, with both 16-bit copies.  The
+    kernel has to take its scalar path for it.  One vmc_adam_cast_multi leaves p, m, v and both copies equal, bit for bit, to
+    vmc_adam_step_dev on 16-byte aligned copies of the same values followed by vmc_cast_weight, and the floats in front of and behind
+    the matrix in all four arenas (and g everywhere) as they were."""
+    from vimo_clip_amd._lib import check, dt, lib, ptr, stream
+    rows, cols, ld, ldt, behind = 68, 132, 192, 128, 7
+    n = rows * cols
+    args = (0.9, 0.999, 1e-8, 0.1, 1)
+    hyp = _hyper()
+    arenas = _adam_buffers(1 + n + behind, 5)
+    before = [a.clone() for a in arenas]
+
+    def copies():
+        return torch.full((rows, ld), 3.0, dtype=dtype, device="cuda"), torch.full((cols, ldt), 3.0, dtype=dtype, device="cuda")
+
+    rp, rg, rm, rv = (a[1:1 + n].clone() for a in arenas)                 # fresh allocations: aligned
+    r16, r16t = copies()
+    assert rp.data_ptr() % 16 == 0
+    check(lib.vmc_adam_step_dev(ptr(rp), ptr(rg), ptr(rm), ptr(rv), n, ptr(hyp), *args, stream()), "adam_step_dev")
+    check(lib.vmc_cast_weight(ptr(rp), ptr(r16), ptr(r16t), rows, cols, ld, ldt, dt(dtype), stream()), "cast_weight")
+
+    w16, w16t = copies()
+    p, g, m, v = arenas
+    assert p.data_ptr() % 16 == 0 and (p.data_ptr() + 4) % 16 == 4
+    tiles_x, tiles_y = (cols + 63) // 64, (rows + 63) // 64
+    desc = torch.tensor([[p.data_ptr() + 4, w16.data_ptr(), w16t.data_ptr(), rows | (cols << 32), ld | (ldt << 32), 0 | (tiles_x << 32)]],
+                        dtype=torch.int64).cuda()
+    check(lib.vmc_adam_cast_multi(ptr(desc), 1, tiles_x * tiles_y, None, 0, 0, ptr(p), ptr(g), ptr(m), ptr(v), ptr(hyp), *args, dt(dtype),
+                                  stream()), "adam_cast_multi")
+    torch.cuda.synchronize()
+
+    def same(a, b):                                                       # the stored bits, not the values
+        as_int = torch.int32 if a.dtype == torch.float32 else torch.int16
+        return torch.equal(a.view(as_int), b.view(as_int))
+    assert not same(rp, before[0][1:1 + n]) and not same(rm, before[2][1:1 + n]) and not same(rv, before[3][1:1 + n])
+    for got, ref in zip((p, m, v), (rp, rm, rv)):
+        assert same(got[1:1 + n], ref)
+    assert same(w16, r16) and same(w16t, r16t)
+    assert bool((w16[:, cols:] == 3.0).all()) and bool((w16t[:, rows:] == 3.0).all())      # the pad columns are not written
+    for got, was in zip(arenas, before):
+        assert same(got[:1], was[:1]) and same(got[1 + n:], was[1 + n:])
+    assert same(g, before[1])
+
+
 # ---- models ---------------------------------------------------------------------------------------------------------------------------
 
 TINY_TFAM = dict(D=256, H=8, L=2, ff=512, C=140, B=4, Tr=16, Tf=15, seed=77)          # the trainer tests' smallest model (test_gpu_grad_clip.py)

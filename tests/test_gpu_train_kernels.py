@@ -21,7 +21,7 @@ DEV = "cuda"
 F32, BF16, F16 = R.F32, R.BF16, R.F16
 DT16 = [BF16, F16]
 DT16_IDS = ["bf16", "f16"]
-E_ARG, E_ALIGN, E_SHAPE = -1, -2, -3
+E_ARG, E_ALIGN, E_SHAPE, E_DTYPE = -1, -2, -3, -4
 EPS = R.LN_EPS
 SENTINEL = 12345.0
 
@@ -543,6 +543,11 @@ def test_set_class_rows(x_f32, dt16):
     else:
         ck_ulp("vmc_set_class_rows", cid, "x", x[:, 0].contiguous(), r64, dt16)
     assert bool((x[:, 1:] == 3.0).all())
+    assert call("vmc_set_class_rows", None, L.ptr(a_d), L.ptr(b_d), Fr, D, N * D, L.dt(xdt), L.dt(dt16), L.stream()) == E_ARG
+    x_d = torch.full((Fr, N, D), 3.0, dtype=xdt, device=DEV)
+    assert call("vmc_set_class_rows", L.ptr(x_d), L.ptr(a_d), L.ptr(b_d), Fr, D, N * D, L.dt(xdt), L.F32, L.stream()) == E_DTYPE
+    sync()
+    assert bool((x_d == 3.0).all())                      # a dtype16 that is no 16-bit type launches nothing
 
 
 # ================================================================================================ dropout masks

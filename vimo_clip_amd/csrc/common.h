@@ -85,6 +85,15 @@ struct F16 {
   }
 };
 
+// The 16-bit type of a C-ABI call: f(BF16{}) or f(F16{}) -- f launches the instantiation for decltype of its argument and returns
+// the entry's result, usually (int)hipGetLastError() -- and VMC_E_DTYPE, with nothing launched, for any other code.
+template <typename F>
+static inline int dispatch16(int dtype16, F&& f) {
+  if (dtype16 == VMC_BF16) return f(BF16{});
+  if (dtype16 == VMC_F16) return f(F16{});
+  return VMC_E_DTYPE;
+}
+
 template <typename T>
 __device__ inline uint32_t pack2(float lo, float hi) {
   return T::pack(lo, hi);

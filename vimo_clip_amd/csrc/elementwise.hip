@@ -2,6 +2,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "weight_tile.h"
 
 extern "C" int vmc_abi_version(void) { return 1; }
 
@@ -132,19 +133,19 @@ static int launch_patches(const patch_src_t<LAYOUT>* src, void* patches, int F, 
   if (!src || !patches || F <= 0 || R <= 0 || p <= 0) return VMC_E_ARG;
   if (R % p || R % 4 || kpad < 3 * p * p || kpad % 8) return VMC_E_SHAPE;
   if ((uintptr_t)src & (4 * sizeof(*src) - 1)) return VMC_E_ALIGN;        // a thread's one load of four pixels
-  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
-  hipStream_t s = (hipStream_t)stream;
-  const int k = 3 * p * p;
-  if (kpad > k) {
-    const size_t rows = (size_t)F * (R / p) * (R / p) * parts;
-    hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
-    VMC_CHECK_LAUNCH();
-  }
-  const size_t total = (size_t)F * CH * R * (R / 4);
-  const auto kernel = dtype16 == VMC_BF16 ? patch_kernel<BF16, LAYOUT, CH> : patch_kernel<F16, LAYOUT, CH>;
-  hipLaunchKernelGGL(kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, (const void*)src, (uint16_t*)patches, F, R, p, kpad, wrap);
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipStream_t s = (hipStream_t)stream;
+    const int k = 3 * p * p;
+    if (kpad > k) {
+      const size_t rows = (size_t)F * (R / p) * (R / p) * parts;
+      hipLaunchKernelGGL(zero_pad_cols_kernel, dim3(grid_for(rows * (kpad - k), 256)), dim3(256), 0, s, (uint16_t*)patches, rows, k, kpad);
+      VMC_CHECK_LAUNCH();
+    }
+    const size_t total = (size_t)F * CH * R * (R / 4);
+    hipLaunchKernelGGL((patch_kernel<decltype(t), LAYOUT, CH>), dim3(grid_for(total, 256)), dim3(256), 0, s, (const void*)src, (uint16_t*)patches,
+                       F, R, p, kpad, wrap);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int vmc_preprocess_patches_u8(const uint8_t* frames, void* patches, int F, int R, int p, int kpad, int wrap_quirk,
@@ -239,80 +240,37 @@ extern "C" int vmc_transpose16(const void* in, void* out, int rows, int cols, in
 }
 
 // ---- f32 weight -> 16-bit (+ transposed copy) ----------------------------------------------------
-template <typename T>
-__global__ void __launch_bounds__(256) cast_weight_kernel(const float* __restrict__ w, uint16_t* __restrict__ w16,
-                                                          uint16_t* __restrict__ w16t, int rows, int cols, size_t ld_out,
-                                                          size_t ld_out_t) {
-  __shared__ uint16_t tile[64][66];
-  const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int i = ty; i < 64; i += 4) {
-    const int r = r0 + i, c = c0 + tx;
-    uint16_t v = 0;
-    if (r < rows && c < cols) {
-      v = T::from_f32(w[(size_t)r * cols + c]);
-      if (w16) w16[(size_t)r * ld_out + c] = v;
-    }
-    tile[i][tx] = v;
-  }
-  if (!w16t) return;
-  __syncthreads();
-  for (int i = ty; i < 64; i += 4) {
-    const int c = c0 + i, r = r0 + tx;
-    if (c < cols && r < rows) w16t[(size_t)c * ld_out_t + r] = tile[tx][i];
-  }
-}
-
-extern "C" int vmc_cast_weight(const float* w, void* w16, void* w16_t, int rows, int cols, int ld_out, int ld_out_t, int dtype16,
-                               void* stream) {
-  if (!w || (!w16 && !w16_t) || rows <= 0 || cols <= 0) return VMC_E_ARG;
-  if ((w16 && ld_out < cols) || (w16_t && ld_out_t < rows)) return VMC_E_ARG;
-  dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(cast_weight_kernel<BF16>, grid, dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)w16, (uint16_t*)w16_t, rows,
-                       cols, (size_t)ld_out, (size_t)ld_out_t);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(cast_weight_kernel<F16>, grid, dim3(256), 0, (hipStream_t)stream, w, (uint16_t*)w16, (uint16_t*)w16_t, rows,
-                       cols, (size_t)ld_out, (size_t)ld_out_t);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
-}
-
-// ---- the same for MANY weights in one launch (after an optimiser step: every cached compute copy of the trained parameters) ----
-// desc[i] = {w, w16, w16t, rows, cols, ld, ldt, tile0, tiles_x}: tensor i owns tiles [tile0, tile0 of i+1) of the 1-D grid.
-struct CastDesc {
-  const float* w;
-  uint16_t* w16;
-  uint16_t* w16t;
-  int rows, cols, ld, ldt, tile0, tiles_x;
-};
-static_assert(sizeof(CastDesc) == 48, "vmc_cast_weights_multi descriptor layout (include/vmc.h)");
-
-template <typename T>
-__global__ void __launch_bounds__(256) cast_weights_multi_kernel(const CastDesc* __restrict__ desc, int n) {
+// One 64 x 64 tile of a matrix (weight_tile.h): every element of the master goes through `u`, is rounded to the 16-bit type T, and
+// leaves as the row-major copy and, through a padded LDS tile, as the transposed copy.  Behind all three kernels below, which differ
+// in how a block finds its matrix and in U:
+//   u.load(x, e)    reads what the update of elements e .. e + 3 needs into the U::Vec x (x.p: the master's four values)
+//   u.update(x, e)  updates x.p and writes back whatever the update changes
+//   u.scalar(e)     both for the one element e; returns the master's value
+// The vector path (tile_vec_ok) issues every load of a thread's four passes before the first update: with the four arrays of AdamW
+// that is 16 float4 per thread.
+template <typename T, typename U>
+__device__ __forceinline__ void weight_tile(const CastDesc& d, int r0, int c0, const U& u) {
   __shared__ uint16_t tile[64][68];             // 136-B rows: 8-byte aligned row starts for the 4-element writes
-  int lo = 0, hi = n - 1;                       // last descriptor whose tile0 <= blockIdx.x
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].tile0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const CastDesc d = desc[lo];
-  const int t = blockIdx.x - d.tile0;
-  const int r0 = (t / d.tiles_x) * 64, c0 = (t % d.tiles_x) * 64;
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;      // 16 x 16 threads, 4 elements each per pass, 4 passes
-  // vector path: 16-byte loads of the master, 8-byte stores of both copies (all of a tensor's rows / strides must allow it)
-  const bool vec = (((uintptr_t)d.w & 15) == 0) && (d.cols & 3) == 0 && (d.rows & 3) == 0 && (!d.w16 || ((d.ld & 3) == 0 && ((uintptr_t)d.w16 & 7) == 0)) &&
-                   (!d.w16t || ((d.ldt & 3) == 0 && ((uintptr_t)d.w16t & 7) == 0));
-  if (vec) {
+  if (tile_vec_ok(d)) {
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;      // 16 x 16 threads, 4 elements each per pass, 4 passes
+    typename U::Vec x[4];
+    bool in[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = r0 + ty + 16 * i, c = c0 + 4 * tx;
+      in[i] = r < d.rows && c < d.cols;
+      // a thread outside the matrix reads the nearest four elements inside it and drops them: a load under a condition would be
+      // waited for before the next one is issued
+      u.load(x[i], (size_t)min(r, d.rows - 1) * d.cols + min(c, d.cols - 4));
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = r0 + ty + 16 * i, c = c0 + 4 * tx;
       uint2 pk = make_uint2(0u, 0u);
-      if (r < d.rows && c < d.cols) {
-        const float4 v = *(const float4*)(d.w + (size_t)r * d.cols + c);
-        pk = make_uint2((uint32_t)T::from_f32(v.x) | ((uint32_t)T::from_f32(v.y) << 16), (uint32_t)T::from_f32(v.z) | ((uint32_t)T::from_f32(v.w) << 16));
+      if (in[i]) {
+        u.update(x[i], (size_t)r * d.cols + c);
+        const float4 p = x[i].p;
+        pk = make_uint2((uint32_t)T::from_f32(p.x) | ((uint32_t)T::from_f32(p.y) << 16), (uint32_t)T::from_f32(p.z) | ((uint32_t)T::from_f32(p.w) << 16));
         if (d.w16) *(uint2*)(d.w16 + (size_t)r * d.ld + c) = pk;
       }
       *(uint2*)&tile[ty + 16 * i][4 * tx] = pk;
@@ -333,12 +291,12 @@ __global__ void __launch_bounds__(256) cast_weights_multi_kernel(const CastDesc*
   const int sx = threadIdx.x & 63, sy = threadIdx.x >> 6;
   for (int i = sy; i < 64; i += 4) {
     const int r = r0 + i, c = c0 + sx;
-    uint16_t v = 0;
+    uint16_t h = 0;
     if (r < d.rows && c < d.cols) {
-      v = T::from_f32(d.w[(size_t)r * d.cols + c]);
-      if (d.w16) d.w16[(size_t)r * d.ld + c] = v;
+      h = T::from_f32(u.scalar((size_t)r * d.cols + c));
+      if (d.w16) d.w16[(size_t)r * d.ld + c] = h;
     }
-    tile[i][sx] = v;
+    tile[i][sx] = h;
   }
   if (!d.w16t) return;
   __syncthreads();
@@ -346,6 +304,65 @@ __global__ void __launch_bounds__(256) cast_weights_multi_kernel(const CastDesc*
     const int c = c0 + i, r = r0 + sx;
     if (c < d.cols && r < d.rows) d.w16t[(size_t)c * d.ldt + r] = tile[sx][i];
   }
+}
+
+struct CastOnly {      // the master is only read
+  struct Vec { float4 p; };
+  const float* w;
+  __device__ void load(Vec& x, size_t e) const { x.p = *(const float4*)(w + e); }
+  __device__ void update(Vec&, size_t) const {}
+  __device__ float scalar(size_t e) const { return w[e]; }
+};
+
+// adam_element on p, g, m, v (the arenas at the master's offset); p, m and v are written back
+struct AdamUpdate {
+  struct Vec { float4 p, g, m, v; };
+  float* p;
+  const float* g;
+  float *m, *v;
+  float lr, b1, b2, eps, wd;
+  int decoupled;
+  float step_size, inv_sqrt_bc2, gscale;
+  __device__ void load(Vec& x, size_t e) const {
+    x.p = *(const float4*)(p + e); x.g = *(const float4*)(g + e); x.m = *(const float4*)(m + e); x.v = *(const float4*)(v + e);
+  }
+  __device__ void update(Vec& x, size_t e) const {
+    float* P = &x.p.x; const float* G = &x.g.x; float* M = &x.m.x; float* V = &x.v.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) adam_element(P[j], G[j], M[j], V[j], lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, gscale);
+    *(float4*)(p + e) = x.p; *(float4*)(m + e) = x.m; *(float4*)(v + e) = x.v;
+  }
+  __device__ float scalar(size_t e) const {
+    float pk = p[e], mk = m[e], vk = v[e];
+    adam_element(pk, g[e], mk, vk, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, gscale);
+    p[e] = pk; m[e] = mk; v[e] = vk;
+    return pk;
+  }
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) cast_weight_kernel(const CastDesc d) {      // one matrix, a 2-D grid of tiles
+  weight_tile<T>(d, blockIdx.y * 64, blockIdx.x * 64, CastOnly{d.w});
+}
+
+extern "C" int vmc_cast_weight(const float* w, void* w16, void* w16_t, int rows, int cols, int ld_out, int ld_out_t, int dtype16,
+                               void* stream) {
+  if (!w || (!w16 && !w16_t) || rows <= 0 || cols <= 0) return VMC_E_ARG;
+  if ((w16 && ld_out < cols) || (w16_t && ld_out_t < rows)) return VMC_E_ARG;
+  const CastDesc d = {w, (uint16_t*)w16, (uint16_t*)w16_t, rows, cols, ld_out, ld_out_t, 0, (cols + 63) / 64};
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(cast_weight_kernel<decltype(t)>, dim3(d.tiles_x, (rows + 63) / 64), dim3(256), 0, (hipStream_t)stream, d);
+    return (int)hipGetLastError();
+  });
+}
+
+// ---- the same for MANY weights in one launch (after an optimiser step: every cached compute copy of the trained parameters) ----
+// Tensor i owns tiles [desc[i].tile0, desc[i + 1].tile0) of the 1-D grid.
+template <typename T>
+__global__ void __launch_bounds__(256) cast_weights_multi_kernel(const CastDesc* __restrict__ desc, int n) {
+  const CastDesc d = desc[owner_of_block(desc, n, (int)blockIdx.x)];
+  const int t = blockIdx.x - d.tile0;
+  weight_tile<T>(d, (t / d.tiles_x) * 64, (t % d.tiles_x) * 64, CastOnly{d.w});
 }
 
 // ---- AdamW update + refresh of the 16-bit copies in ONE pass over the masters (captured training steps) -----------------------
@@ -359,105 +376,24 @@ __global__ void __launch_bounds__(256) adam_cast_multi_kernel(const CastDesc* __
                                                               const float* __restrict__ g_base, float* __restrict__ m_base,
                                                               float* __restrict__ v_base, const float* __restrict__ hyper, float b1, float b2,
                                                               float eps, float wd, int decoupled, const int* __restrict__ skip) {
-  __shared__ uint16_t tile[64][68];
   if (skip != nullptr && *skip != 0) return;      // a skipped step: masters, moments and 16-bit copies keep their bytes
   const float lr = hyper[0], step_size = hyper[1], inv_sqrt_bc2 = hyper[2], gscale = hyper[3];
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[mid].tile0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const CastDesc d = desc[lo];
+  const CastDesc d = desc[owner_of_block(desc, n, (int)blockIdx.x)];
   const int t = blockIdx.x - d.tile0;
-  const int r0 = (t / d.tiles_x) * 64, c0 = (t % d.tiles_x) * 64;
-  float* const w = const_cast<float*>(d.w);
   const size_t base = (size_t)(d.w - p_base);
-  const float* const g = g_base + base;
-  float* const m = m_base + base;
-  float* const v = v_base + base;
-  const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const bool vec = (d.cols & 3) == 0 && (d.rows & 3) == 0 && (!d.w16 || ((d.ld & 3) == 0 && ((uintptr_t)d.w16 & 7) == 0)) &&
-                   (!d.w16t || ((d.ldt & 3) == 0 && ((uintptr_t)d.w16t & 7) == 0));       // arena slots are 256-byte aligned
-  if (vec) {
-    float4 pp[4], gg[4], mm[4], vv[4];
-    bool in[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {       // all loads of the tile first: 16 float4 in flight per thread
-      const int r = r0 + ty + 16 * i, c = c0 + 4 * tx;
-      in[i] = r < d.rows && c < d.cols;
-      if (in[i]) {
-        const size_t e = (size_t)r * d.cols + c;
-        pp[i] = *(const float4*)(w + e); gg[i] = *(const float4*)(g + e); mm[i] = *(const float4*)(m + e); vv[i] = *(const float4*)(v + e);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = r0 + ty + 16 * i, c = c0 + 4 * tx;
-      uint2 pk = make_uint2(0u, 0u);
-      if (in[i]) {
-        float* P = &pp[i].x; const float* G = &gg[i].x; float* M = &mm[i].x; float* V = &vv[i].x;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) adam_element(P[j], G[j], M[j], V[j], lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, gscale);
-        const size_t e = (size_t)r * d.cols + c;
-        *(float4*)(w + e) = pp[i]; *(float4*)(m + e) = mm[i]; *(float4*)(v + e) = vv[i];
-        pk = make_uint2((uint32_t)T::from_f32(P[0]) | ((uint32_t)T::from_f32(P[1]) << 16), (uint32_t)T::from_f32(P[2]) | ((uint32_t)T::from_f32(P[3]) << 16));
-        if (d.w16) *(uint2*)(d.w16 + (size_t)r * d.ld + c) = pk;
-      }
-      *(uint2*)&tile[ty + 16 * i][4 * tx] = pk;
-    }
-    if (!d.w16t) return;
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = c0 + ty + 16 * i, r = r0 + 4 * tx;
-      if (c < d.cols && r < d.rows) {
-        const int cl = ty + 16 * i;
-        *(uint2*)(d.w16t + (size_t)c * d.ldt + r) = make_uint2((uint32_t)tile[4 * tx][cl] | ((uint32_t)tile[4 * tx + 1][cl] << 16),
-                                                              (uint32_t)tile[4 * tx + 2][cl] | ((uint32_t)tile[4 * tx + 3][cl] << 16));
-      }
-    }
-    return;
-  }
-  const int sx = threadIdx.x & 63, sy = threadIdx.x >> 6;
-  for (int i = sy; i < 64; i += 4) {
-    const int r = r0 + i, c = c0 + sx;
-    uint16_t h = 0;
-    if (r < d.rows && c < d.cols) {
-      const size_t e = (size_t)r * d.cols + c;
-      float pk = w[e], mk = m[e], vk = v[e];
-      adam_element(pk, g[e], mk, vk, lr, b1, b2, eps, wd, decoupled, step_size, inv_sqrt_bc2, gscale);
-      w[e] = pk; m[e] = mk; v[e] = vk;
-      h = T::from_f32(pk);
-      if (d.w16) d.w16[(size_t)r * d.ld + c] = h;
-    }
-    tile[i][sx] = h;
-  }
-  if (!d.w16t) return;
-  __syncthreads();
-  for (int i = sy; i < 64; i += 4) {
-    const int c = c0 + i, r = r0 + sx;
-    if (c < d.cols && r < d.rows) d.w16t[(size_t)c * d.ldt + r] = tile[sx][i];
-  }
+  weight_tile<T>(d, (t / d.tiles_x) * 64, (t % d.tiles_x) * 64,
+                 AdamUpdate{const_cast<float*>(d.w), g_base + base, m_base + base, v_base + base, lr, b1, b2, eps, wd, decoupled, step_size,
+                            inv_sqrt_bc2, gscale});
 }
 
-// the parameters without compute copies: ranges[i] = {offset into the arenas, elements, first block}; 1024 elements per block
-struct AdamRange {
-  unsigned long long off;
-  int n, block0;
-};
-static_assert(sizeof(AdamRange) == 16, "vmc_adam_cast_multi range layout (include/vmc.h)");
+// the parameters without compute copies: 1024 elements per block
 __global__ void __launch_bounds__(256) adam_ranges_kernel(const AdamRange* __restrict__ rr, int n, float* __restrict__ p_base,
                                                           const float* __restrict__ g_base, float* __restrict__ m_base,
                                                           float* __restrict__ v_base, const float* __restrict__ hyper, float b1, float b2, float eps,
                                                           float wd, int decoupled, const int* __restrict__ skip) {
   if (skip != nullptr && *skip != 0) return;
   const float lr = hyper[0], step_size = hyper[1], inv_sqrt_bc2 = hyper[2], gscale = hyper[3];
-  int lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (rr[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
-  }
-  const AdamRange r = rr[lo];
+  const AdamRange r = rr[owner_of_block(rr, n, (int)blockIdx.x)];
   const int i0 = ((int)blockIdx.x - r.block0) * 1024 + 4 * threadIdx.x;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -478,16 +414,13 @@ extern "C" int vmc_adam_cast_multi_skip(const void* desc, int n_desc, int total_
   if ((n_desc > 0) != (desc != nullptr && total_tiles > 0) || (n_ranges > 0) != (ranges != nullptr && total_range_blocks > 0)) return VMC_E_ARG;
   if (((uintptr_t)p_base | (uintptr_t)g_base | (uintptr_t)m_base | (uintptr_t)v_base | (uintptr_t)hyper) & 15) return VMC_E_ALIGN;
   if ((uintptr_t)skip & 3) return VMC_E_ALIGN;
-  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
-  if (n_desc > 0) {
-    if (dtype16 == VMC_BF16)
-      hipLaunchKernelGGL(adam_cast_multi_kernel<BF16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc, p_base,
-                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
-    else
-      hipLaunchKernelGGL(adam_cast_multi_kernel<F16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc, p_base,
-                         g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
-    VMC_CHECK_LAUNCH();
-  }
+  const int rc = dispatch16(dtype16, [&](auto t) {
+    if (n_desc <= 0) return 0;
+    hipLaunchKernelGGL(adam_cast_multi_kernel<decltype(t)>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc,
+                       p_base, g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
+    return (int)hipGetLastError();
+  });
+  if (rc) return rc;
   if (n_ranges > 0) {
     hipLaunchKernelGGL(adam_ranges_kernel, dim3(total_range_blocks), dim3(256), 0, (hipStream_t)stream, (const AdamRange*)ranges, n_ranges, p_base,
                        g_base, m_base, v_base, hyper, beta1, beta2, eps, weight_decay, decoupled_wd, skip);
@@ -505,14 +438,10 @@ extern "C" int vmc_adam_cast_multi(const void* desc, int n_desc, int total_tiles
 
 extern "C" int vmc_cast_weights_multi(const void* desc, int n_desc, int total_tiles, int dtype16, void* stream) {
   if (!desc || n_desc <= 0 || total_tiles <= 0) return VMC_E_ARG;
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(cast_weights_multi_kernel<BF16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(cast_weights_multi_kernel<F16>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(cast_weights_multi_kernel<decltype(t)>, dim3(total_tiles), dim3(256), 0, (hipStream_t)stream, (const CastDesc*)desc, n_desc);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- column sums (bias gradients): partials per row-slab, then a reduce ---------------------------
@@ -585,11 +514,12 @@ extern "C" int vmc_colsum(const void* in, float* out, int M, int N, int ld_in, i
   const int slabs = colsum_slabs(M);
   dim3 grid((N / 4 + 63) / 64, slabs);
   hipStream_t s = (hipStream_t)stream;
-  if (in_dtype == VMC_F16)
-    hipLaunchKernelGGL(colsum_partial_kernel<F16>, grid, dim3(256), 0, s, in, (float*)workspace, M, N, (size_t)ld_in, 0);
-  else
-    hipLaunchKernelGGL(colsum_partial_kernel<BF16>, grid, dim3(256), 0, s, in, (float*)workspace, M, N, (size_t)ld_in, in_dtype == VMC_F32);
-  VMC_CHECK_LAUNCH();
+  const int in_f32 = in_dtype == VMC_F32;      // f32 input: the 16-bit type of the instantiation is not used
+  const int rc = dispatch16(in_f32 ? VMC_BF16 : in_dtype, [&](auto t) {
+    hipLaunchKernelGGL(colsum_partial_kernel<decltype(t)>, grid, dim3(256), 0, s, in, (float*)workspace, M, N, (size_t)ld_in, in_f32);
+    return (int)hipGetLastError();
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((N + 63) / 64), dim3(256), 0, s, (const float*)workspace, out, slabs, N);
   VMC_CHECK_LAUNCH();
   return 0;
@@ -612,12 +542,10 @@ extern "C" int vmc_set_class_rows(void* x, const float* a, const float* b, int F
                                   void* stream) {
   if (!x || !a || !b || F <= 0 || D <= 0) return VMC_E_ARG;
   const int grid = grid_for((size_t)F * D, 256);
-  if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(set_class_rows_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, a, b, F, D, row_stride, x_dtype == VMC_F32);
-  else
-    hipLaunchKernelGGL(set_class_rows_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, a, b, F, D, row_stride, x_dtype == VMC_F32);
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(set_class_rows_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, a, b, F, D, row_stride, x_dtype == VMC_F32);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- activations on flat 16-bit arrays (training path) ---------------------------------------------
@@ -671,21 +599,19 @@ extern "C" int vmc_act_fwd(const void* x, void* y, size_t n, int act, int dtype1
   if (!x || !y || n == 0) return VMC_E_ARG;
   if (((uintptr_t)x | (uintptr_t)y) & 15) return VMC_E_ALIGN;
   const int grid = grid_for((n + 7) / 8, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(act_fwd_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, n, act);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(act_fwd_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, n, act);
-  else return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(act_fwd_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (uint16_t*)y, n, act);
+    return (int)hipGetLastError();
+  });
 }
 extern "C" int vmc_act_bwd(const void* x, const void* dy, void* dx, size_t n, int act, int dtype16, void* stream) {
   if (!x || !dy || !dx || n == 0) return VMC_E_ARG;
   if (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) return VMC_E_ALIGN;
   const int grid = grid_for((n + 7) / 8, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(act_bwd_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)dy, (uint16_t*)dx, n, act);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(act_bwd_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)dy, (uint16_t*)dx, n, act);
-  else return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(act_bwd_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, (const uint16_t*)dy, (uint16_t*)dx, n, act);
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- mean over T ----------------------------------------------------------------------------------
@@ -712,11 +638,10 @@ extern "C" int vmc_mean_pool_len(const void* x, void* out16, float* out32, int B
                                  void* stream) {
   if (!x || (!out16 && !out32) || B <= 0 || Tn <= 0 || D <= 0) return VMC_E_ARG;
   const int grid = grid_for((size_t)B * D, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(mean_pool_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32, pool_len);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(mean_pool_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32, pool_len);
-  else return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(mean_pool_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)out16, out32, B, Tn, D, x_dtype == VMC_F32, pool_len);
+    return (int)hipGetLastError();
+  });
 }
 
 extern "C" int vmc_mean_pool(const void* x, void* out16, float* out32, int B, int Tn, int D, int x_dtype, int dtype16, void* stream) {
@@ -785,19 +710,17 @@ extern "C" int vmc_cast_f32_to_16(const float* x, void* y, size_t n, int dtype16
   if (!x || !y || n == 0) return VMC_E_ARG;
   if (((uintptr_t)x & 15) | ((uintptr_t)y & 7)) return VMC_E_ALIGN;
   const int grid = grid_for((n + 3) / 4, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(cast_to16_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, n);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(cast_to16_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, n);
-  else return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(cast_to16_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y, n);
+    return (int)hipGetLastError();
+  });
 }
 extern "C" int vmc_cast_16_to_f32(const void* x, float* y, size_t n, int dtype16, void* stream) {
   if (!x || !y || n == 0) return VMC_E_ARG;
   if (((uintptr_t)y & 15) | ((uintptr_t)x & 7)) return VMC_E_ALIGN;
   const int grid = grid_for((n + 3) / 4, 256);
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(cast_to32_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, y, n);
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(cast_to32_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, y, n);
-  else return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(cast_to32_kernel<decltype(t)>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, y, n);
+    return (int)hipGetLastError();
+  });
 }

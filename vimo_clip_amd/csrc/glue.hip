@@ -11,13 +11,6 @@ __device__ inline void st1(void* p, size_t i, bool f32, float v) {
   else ((uint16_t*)p)[i] = T::from_f32(v);
 }
 
-#define VMC_DISPATCH16(KERNEL, GRID, ...)                                                                      \
-  if (dtype16 == VMC_F16) hipLaunchKernelGGL(KERNEL<F16>, dim3(GRID), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-  else if (dtype16 == VMC_BF16) hipLaunchKernelGGL(KERNEL<BF16>, dim3(GRID), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
-  else return VMC_E_DTYPE;                                                                                     \
-  VMC_CHECK_LAUNCH();                                                                                          \
-  return 0;
-
 // y = a + b  (sum of the two gradients that meet at a fork), any mix of f32 / 16-bit
 template <typename T>
 __global__ void add_kernel(const void* __restrict__ a, const void* __restrict__ b, void* __restrict__ y, size_t n, int a_f32, int b_f32,
@@ -27,7 +20,11 @@ __global__ void add_kernel(const void* __restrict__ a, const void* __restrict__ 
 }
 extern "C" int vmc_add(const void* a, const void* b, void* y, size_t n, int a_dtype, int b_dtype, int y_dtype, int dtype16, void* stream) {
   if (!a || !b || !y || n == 0) return VMC_E_ARG;
-  VMC_DISPATCH16(add_kernel, grid_for(n, 256), a, b, y, n, a_dtype == VMC_F32, b_dtype == VMC_F32, y_dtype == VMC_F32)
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(add_kernel<decltype(t)>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, y, n, a_dtype == VMC_F32,
+                       b_dtype == VMC_F32, y_dtype == VMC_F32);
+    return (int)hipGetLastError();
+  });
 }
 
 // dx[b,t,:] = dout[b,:] / n on the n pooled rows, 0 on rows n..T-1   (backward of vmc_mean_pool_len; n = T without a pool length)
@@ -47,7 +44,11 @@ __global__ void mean_pool_bwd_kernel(const void* __restrict__ dout, void* __rest
 extern "C" int vmc_mean_pool_bwd_len(const void* dout, void* dx, int B, int Tn, int D, const int* pool_len, int dout_dtype, int dx_dtype, int dtype16,
                                      void* stream) {
   if (!dout || !dx || B <= 0 || Tn <= 0 || D <= 0) return VMC_E_ARG;
-  VMC_DISPATCH16(mean_pool_bwd_kernel, grid_for((size_t)B * Tn * D, 256), dout, dx, B, Tn, D, dout_dtype == VMC_F32, dx_dtype == VMC_F32, pool_len)
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(mean_pool_bwd_kernel<decltype(t)>, dim3(grid_for((size_t)B * Tn * D, 256)), dim3(256), 0, (hipStream_t)stream, dout, dx, B,
+                       Tn, D, dout_dtype == VMC_F32, dx_dtype == VMC_F32, pool_len);
+    return (int)hipGetLastError();
+  });
 }
 extern "C" int vmc_mean_pool_bwd(const void* dout, void* dx, int B, int Tn, int D, int dout_dtype, int dx_dtype, int dtype16, void* stream) {
   return vmc_mean_pool_bwd_len(dout, dx, B, Tn, D, nullptr, dout_dtype, dx_dtype, dtype16, stream);
@@ -69,7 +70,11 @@ __global__ void assemble_tokens_kernel(const uint16_t* __restrict__ xp, const fl
 extern "C" int vmc_assemble_tokens(const void* xp, const float* cls, const float* pos, void* x, int F, int N, int D, int x_dtype,
                                    int dtype16, void* stream) {
   if (!xp || !cls || !pos || !x || F <= 0 || N <= 1 || D <= 0) return VMC_E_ARG;
-  VMC_DISPATCH16(assemble_tokens_kernel, grid_for((size_t)F * N * D, 256), (const uint16_t*)xp, cls, pos, x, F, N, D, x_dtype == VMC_F32)
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(assemble_tokens_kernel<decltype(t)>, dim3(grid_for((size_t)F * N * D, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)xp, cls, pos, x, F, N, D, x_dtype == VMC_F32);
+    return (int)hipGetLastError();
+  });
 }
 
 // Inverted dropout with a counter-based keep mask: keep(i) = hash(seed, i) >= p; y = x * keep / (1 - p).
@@ -107,18 +112,15 @@ __global__ void __launch_bounds__(256) dropout16x8_kernel(const uint4* __restric
 }
 extern "C" int vmc_dropout(const void* x, void* y, size_t n, float p, uint64_t seed, int x_dtype, int dtype16, void* stream) {
   if (!x || !y || n == 0 || p < 0.f || p >= 1.f) return VMC_E_ARG;
-  if (x_dtype != VMC_F32 && (n & 7) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0) {
-    const int grid = grid_for(n / 8, 256, 256 * 32);
-    if (dtype16 == VMC_BF16)
-      hipLaunchKernelGGL(dropout16x8_kernel<BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y, n / 8, p, seed);
-    else if (dtype16 == VMC_F16)
-      hipLaunchKernelGGL(dropout16x8_kernel<F16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y, n / 8, p, seed);
+  return dispatch16(dtype16, [&](auto t) {
+    using T = decltype(t);
+    if (x_dtype != VMC_F32 && (n & 7) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
+      hipLaunchKernelGGL(dropout16x8_kernel<T>, dim3(grid_for(n / 8, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, (const uint4*)x, (uint4*)y,
+                         n / 8, p, seed);
     else
-      return VMC_E_DTYPE;
-    VMC_CHECK_LAUNCH();
-    return 0;
-  }
-  VMC_DISPATCH16(dropout_kernel, grid_for(n, 256), x, y, n, p, seed, x_dtype == VMC_F32)
+      hipLaunchKernelGGL(dropout_kernel<T>, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, p, seed, x_dtype == VMC_F32);
+    return (int)hipGetLastError();
+  });
 }
 
 // y16 = cast(x32 * keep1/(1-p1) * keep2/(1-p2)): the gradient of a branch that went through one or two dropouts in front of a post-norm
@@ -150,14 +152,11 @@ __global__ void cast_dropout2_kernel(const float* __restrict__ x, uint16_t* __re
 extern "C" int vmc_cast_dropout2(const float* x, void* y16, size_t n, float p1, uint64_t seed1, float p2, uint64_t seed2, int dtype16,
                                  void* stream) {
   if (!x || !y16 || n == 0 || p1 < 0.f || p1 >= 1.f || p2 < 0.f || p2 >= 1.f) return VMC_E_ARG;
-  if (dtype16 == VMC_BF16)
-    hipLaunchKernelGGL(cast_dropout2_kernel<BF16>, dim3(grid_for((n + 7) / 8, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y16, n, p1, seed1, p2, seed2);
-  else if (dtype16 == VMC_F16)
-    hipLaunchKernelGGL(cast_dropout2_kernel<F16>, dim3(grid_for((n + 7) / 8, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, x, (uint16_t*)y16, n, p1, seed1, p2, seed2);
-  else
-    return VMC_E_DTYPE;
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    hipLaunchKernelGGL(cast_dropout2_kernel<decltype(t)>, dim3(grid_for((n + 7) / 8, 256, 256 * 32)), dim3(256), 0, (hipStream_t)stream, x,
+                       (uint16_t*)y16, n, p1, seed1, p2, seed2);
+    return (int)hipGetLastError();
+  });
 }
 
 // y = x * (*scale)   with the scale read from device memory (incoming scalar gradient of a loss)

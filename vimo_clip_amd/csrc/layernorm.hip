@@ -1,7 +1,12 @@
 // LayerNorm forward / backward, one wave per row, fp32 statistics (gfx950).  HBM-bound: 16-byte loads.
+#include <type_traits>
+
 #include "common.h"
 
 #define LN_MAX_CHUNKS 16  // D <= 16 * 256 = 4096
+// the float4 chunks per lane of a launch, as a type: the launchers pick the kernel instantiation from the run-time D with it
+template <int N>
+using chunks = std::integral_constant<int, N>;
 
 template <typename T>
 __device__ inline float4 load4(const void* base, size_t idx, bool is_f32) {
@@ -97,24 +102,18 @@ extern "C" int vmc_layernorm_fwd(const void* x, const float* gamma, const float*
   if (ldx % 4 || ldx < D) return VMC_E_ALIGN;
   if (x_dtype != VMC_F32 && x_dtype != dtype16) return VMC_E_DTYPE;
   const int grid = grid_for((size_t)rows, 4, 256 * 8);
-  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
-#define VMC_LN_FWD(NCH)                                                                                                     \
-  do {                                                                                                                      \
-    if (dtype16 == VMC_BF16)                                                                                                \
-      hipLaunchKernelGGL((ln_fwd_kernel<BF16, NCH>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,          \
-                         (uint16_t*)y16, y32, mean, rstd, rows, D, (size_t)ldx, eps, x_dtype == VMC_F32);                    \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((ln_fwd_kernel<F16, NCH>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,           \
-                         (uint16_t*)y16, y32, mean, rstd, rows, D, (size_t)ldx, eps, x_dtype == VMC_F32);                    \
-  } while (0)
-  if (D <= 512) VMC_LN_FWD(2);
-  else if (D <= 768) VMC_LN_FWD(3);
-  else if (D <= 1024) VMC_LN_FWD(4);
-  else if (D <= 2048) VMC_LN_FWD(8);
-  else VMC_LN_FWD(LN_MAX_CHUNKS);
-#undef VMC_LN_FWD
-  VMC_CHECK_LAUNCH();
-  return 0;
+  return dispatch16(dtype16, [&](auto t) {
+    auto launch = [&](auto nch) {
+      hipLaunchKernelGGL((ln_fwd_kernel<decltype(t), decltype(nch)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
+                         (uint16_t*)y16, y32, mean, rstd, rows, D, (size_t)ldx, eps, x_dtype == VMC_F32);
+    };
+    if (D <= 512) launch(chunks<2>{});
+    else if (D <= 768) launch(chunks<3>{});
+    else if (D <= 1024) launch(chunks<4>{});
+    else if (D <= 2048) launch(chunks<8>{});
+    else launch(chunks<LN_MAX_CHUNKS>{});
+    return (int)hipGetLastError();
+  });
 }
 
 // ---- fused residual add + LayerNorm ---------------------------------------------------------------
@@ -188,20 +187,20 @@ template <typename T>
 static int launch_add_ln(float* x, const void* branch0, const void* branch, const float* gamma, const float* beta, void* y16, int rows,
                          int D, size_t ldx, size_t ldb0, size_t ldb, float eps, int write_x, hipStream_t s) {
   const int grid = grid_for((size_t)rows, 4, 256 * 8);
-#define VMC_ADDLN(CHN)                                                                                                        \
-  hipLaunchKernelGGL((add_ln_kernel<T, CHN>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch0, (const uint16_t*)branch, gamma, \
-                     beta, (uint16_t*)y16, rows, ldx, ldb0, ldb, eps, write_x)
+  auto launch = [&](auto ch) {
+    hipLaunchKernelGGL((add_ln_kernel<T, decltype(ch)::value>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch0, (const uint16_t*)branch,
+                       gamma, beta, (uint16_t*)y16, rows, ldx, ldb0, ldb, eps, write_x);
+  };
   switch (D / 256) {
-    case 1: VMC_ADDLN(1); break;
-    case 2: VMC_ADDLN(2); break;
-    case 3: VMC_ADDLN(3); break;
-    case 4: VMC_ADDLN(4); break;
-    case 5: VMC_ADDLN(5); break;
-    case 6: VMC_ADDLN(6); break;
-    case 8: VMC_ADDLN(8); break;
+    case 1: launch(chunks<1>{}); break;
+    case 2: launch(chunks<2>{}); break;
+    case 3: launch(chunks<3>{}); break;
+    case 4: launch(chunks<4>{}); break;
+    case 5: launch(chunks<5>{}); break;
+    case 6: launch(chunks<6>{}); break;
+    case 8: launch(chunks<8>{}); break;
     default: return VMC_E_SHAPE;
   }
-#undef VMC_ADDLN
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -211,9 +210,9 @@ extern "C" int vmc_add_layernorm_fwd(float* x, const void* branch, const float* 
   if (!x || !branch || !gamma || !beta || !y16 || rows <= 0 || D <= 0) return VMC_E_ARG;
   if (D % 256 || D > 2048) return VMC_E_SHAPE;
   if (ldx % 4 || ldb % 4 || ldx < D || ldb < D) return VMC_E_ALIGN;
-  if (dtype16 == VMC_BF16) return launch_add_ln<BF16>(x, nullptr, branch, gamma, beta, y16, rows, D, ldx, 0, ldb, eps, write_x, (hipStream_t)stream);
-  if (dtype16 == VMC_F16) return launch_add_ln<F16>(x, nullptr, branch, gamma, beta, y16, rows, D, ldx, 0, ldb, eps, write_x, (hipStream_t)stream);
-  return VMC_E_DTYPE;
+  return dispatch16(dtype16, [&](auto t) {
+    return launch_add_ln<decltype(t)>(x, nullptr, branch, gamma, beta, y16, rows, D, ldx, 0, ldb, eps, write_x, (hipStream_t)stream);
+  });
 }
 
 extern "C" int vmc_add2_layernorm_fwd(float* x, const void* branch0, const void* branch, const float* gamma, const float* beta, void* y16,
@@ -221,11 +220,9 @@ extern "C" int vmc_add2_layernorm_fwd(float* x, const void* branch0, const void*
   if (!x || !branch0 || !branch || !gamma || !beta || !y16 || rows <= 0 || D <= 0) return VMC_E_ARG;
   if (D % 256 || D > 2048) return VMC_E_SHAPE;
   if (ldx % 4 || ldb0 % 4 || ldb % 4 || ldx < D || ldb0 < D || ldb < D) return VMC_E_ALIGN;
-  if (dtype16 == VMC_BF16)
-    return launch_add_ln<BF16>(x, branch0, branch, gamma, beta, y16, rows, D, ldx, ldb0, ldb, eps, write_x, (hipStream_t)stream);
-  if (dtype16 == VMC_F16)
-    return launch_add_ln<F16>(x, branch0, branch, gamma, beta, y16, rows, D, ldx, ldb0, ldb, eps, write_x, (hipStream_t)stream);
-  return VMC_E_DTYPE;
+  return dispatch16(dtype16, [&](auto t) {
+    return launch_add_ln<decltype(t)>(x, branch0, branch, gamma, beta, y16, rows, D, ldx, ldb0, ldb, eps, write_x, (hipStream_t)stream);
+  });
 }
 
 // ---- post-norm block tail: s = x + branch; y = LN(s) written as fp32 (next residual operand) and 16-bit (next GEMM
@@ -305,19 +302,19 @@ static int launch_postnorm(const float* x, const void* branch, const float* gamm
                            void* y16, float* mean, float* rstd, int rows, int D, float eps, float p1, uint64_t seed1, float p2,
                            uint64_t seed2, hipStream_t s) {
   const int grid = grid_for((size_t)rows, 4, 256 * 8);
-#define VMC_PN(CHN)                                                                                                          \
-  hipLaunchKernelGGL((postnorm_kernel<T, CHN>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch, gamma, beta, sum_out, y32, \
-                     (uint16_t*)y16, mean, rstd, rows, eps, p1, seed1, p2, seed2)
+  auto launch = [&](auto ch) {
+    hipLaunchKernelGGL((postnorm_kernel<T, decltype(ch)::value>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch, gamma, beta, sum_out,
+                       y32, (uint16_t*)y16, mean, rstd, rows, eps, p1, seed1, p2, seed2);
+  };
   switch (D / 256) {
-    case 1: VMC_PN(1); break;
-    case 2: VMC_PN(2); break;
-    case 3: VMC_PN(3); break;
-    case 4: VMC_PN(4); break;
-    case 6: VMC_PN(6); break;
-    case 8: VMC_PN(8); break;
+    case 1: launch(chunks<1>{}); break;
+    case 2: launch(chunks<2>{}); break;
+    case 3: launch(chunks<3>{}); break;
+    case 4: launch(chunks<4>{}); break;
+    case 6: launch(chunks<6>{}); break;
+    case 8: launch(chunks<8>{}); break;
     default: return VMC_E_SHAPE;
   }
-#undef VMC_PN
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -328,13 +325,10 @@ extern "C" int vmc_postnorm_dropout_fwd(const float* x, const void* branch, cons
   if (!x || !branch || !gamma || !beta || (!y32 && !y16) || rows <= 0 || D <= 0) return VMC_E_ARG;
   if (D % 256 || D > 2048) return VMC_E_SHAPE;
   if (drop_p1 < 0.f || drop_p1 >= 1.f || drop_p2 < 0.f || drop_p2 >= 1.f || (drop_p2 > 0.f && drop_p1 <= 0.f)) return VMC_E_ARG;
-  if (dtype16 == VMC_BF16)
-    return launch_postnorm<BF16>(x, branch, gamma, beta, sum_out, y32, y16, mean, rstd, rows, D, eps, drop_p1, drop_seed1, drop_p2,
-                                 drop_seed2, (hipStream_t)stream);
-  if (dtype16 == VMC_F16)
-    return launch_postnorm<F16>(x, branch, gamma, beta, sum_out, y32, y16, mean, rstd, rows, D, eps, drop_p1, drop_seed1, drop_p2,
-                                drop_seed2, (hipStream_t)stream);
-  return VMC_E_DTYPE;
+  return dispatch16(dtype16, [&](auto t) {
+    return launch_postnorm<decltype(t)>(x, branch, gamma, beta, sum_out, y32, y16, mean, rstd, rows, D, eps, drop_p1, drop_seed1, drop_p2,
+                                        drop_seed2, (hipStream_t)stream);
+  });
 }
 
 extern "C" int vmc_postnorm_fwd(const float* x, const void* branch, const float* gamma, const float* beta, float* sum_out, float* y32,
@@ -541,24 +535,19 @@ static int ln_bwd_impl(const void* dy, const void* dy2, const void* x, const flo
   const int grid = ln_bwd_grid(rows);
   const size_t lds = (size_t)8 * D * sizeof(float);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype16 != VMC_BF16 && dtype16 != VMC_F16) return VMC_E_DTYPE;
-#define VMC_LN_BWD(NCH)                                                                                                          \
-  do {                                                                                                                           \
-    if (dtype16 == VMC_BF16)                                                                                                     \
-      hipLaunchKernelGGL((ln_bwd_kernel<BF16, NCH>), dim3(grid), dim3(256), lds, s, dy, dy2, x, gamma, mean, rstd, dx, add,      \
-                         (float*)workspace, rows, D, (size_t)ldx, dy_dtype == VMC_F32, x_dtype == VMC_F32, dx_dtype == VMC_F32,  \
-                         (uint16_t*)dx16, p1, seed1, p2, seed2);                                                                 \
-    else                                                                                                                         \
-      hipLaunchKernelGGL((ln_bwd_kernel<F16, NCH>), dim3(grid), dim3(256), lds, s, dy, dy2, x, gamma, mean, rstd, dx, add,       \
-                         (float*)workspace, rows, D, (size_t)ldx, dy_dtype == VMC_F32, x_dtype == VMC_F32, dx_dtype == VMC_F32,  \
-                         (uint16_t*)dx16, p1, seed1, p2, seed2);                                                                 \
-  } while (0)
-  if (D <= 512) VMC_LN_BWD(2);
-  else if (D <= 768) VMC_LN_BWD(3);
-  else if (D <= 1024) VMC_LN_BWD(4);
-  else VMC_LN_BWD(LN_BWD_MAX_CHUNKS);
-#undef VMC_LN_BWD
-  VMC_CHECK_LAUNCH();
+  const int rc = dispatch16(dtype16, [&](auto t) {
+    auto launch = [&](auto nch) {
+      hipLaunchKernelGGL((ln_bwd_kernel<decltype(t), decltype(nch)::value>), dim3(grid), dim3(256), lds, s, dy, dy2, x, gamma, mean, rstd, dx, add,
+                         (float*)workspace, rows, D, (size_t)ldx, dy_dtype == VMC_F32, x_dtype == VMC_F32, dx_dtype == VMC_F32,
+                         (uint16_t*)dx16, p1, seed1, p2, seed2);
+    };
+    if (D <= 512) launch(chunks<2>{});
+    else if (D <= 768) launch(chunks<3>{});
+    else if (D <= 1024) launch(chunks<4>{});
+    else launch(chunks<LN_BWD_MAX_CHUNKS>{});
+    return (int)hipGetLastError();
+  });
+  if (rc) return rc;
   hipLaunchKernelGGL(ln_reduce_strided_kernel, dim3((D + 15) / 16, 2), dim3(256), 0, s, (const float*)workspace, dgamma, dbeta, grid, D);
   VMC_CHECK_LAUNCH();
   return 0;
