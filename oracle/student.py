@@ -18,18 +18,19 @@ def residual_mlp(sd, x, alpha, prefix="residual_mlp."):
     return x + alpha * (h @ sd[prefix + "fc2.weight"].t() + sd[prefix + "fc2.bias"])
 
 
-def student_forward(sd, flow_videos_u8, heads, alpha=0.1, wrap_quirk=True):
+def student_forward(sd, flow_videos_u8, heads, alpha=0.1, wrap_quirk=True, dtype=torch.float32):
     """models/student_model.py:61-98.  flow_videos [B,T,3,H,W] u8 with H=W=input resolution.
 
     Returns (embeddings [B,T,E], embeddings_for_distillation [B,T,E], logits [B,C]).
     ``wrap_quirk`` reproduces the float->to_pil_image wrap-around of :74,:78.
+    ``dtype``: the arithmetic's type (the state dict must hold it; float64 for the float64 references of the tests).
     """
     B, T, C, H, W = flow_videos_u8.shape
     frames = flow_videos_u8.reshape(B * T, C, H, W)
     if wrap_quirk:
         frames = vit.to_pil_wrap_u8(frames)
-    pix = vit.normalize_u8(frames)
-    emb = vit.vit_forward(sd, pix, heads, prefix="visual_encoder.").view(B, T, -1)   # :84-87
+    pix = vit.normalize_u8(frames, dtype)
+    emb = vit.vit_forward(sd, pix, heads, prefix="visual_encoder.", dtype=dtype).view(B, T, -1)   # :84-87
     emb_d = residual_mlp(sd, emb, alpha)                                               # :90
     pooled = emb.mean(dim=1)                                                           # :93
     h = torch.relu(pooled @ sd["classification_head.0.weight"].t() + sd["classification_head.0.bias"])

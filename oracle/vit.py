@@ -19,13 +19,13 @@ CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
-def normalize_u8(frames_u8: torch.Tensor) -> torch.Tensor:
+def normalize_u8(frames_u8: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """[F,3,H,W] u8 -> f32 (x/255 - mean)/std.  ToTensor + Normalize of clip._transform and the
     rescale+normalize of CLIPImageProcessor (extract_embeddings.py:91); for H=W=224 the bicubic
-    resize / centre crop in front of it are identities."""
-    x = frames_u8.to(torch.float32) / 255.0
-    mean = torch.tensor(CLIP_MEAN, dtype=torch.float32).view(1, 3, 1, 1)
-    std = torch.tensor(CLIP_STD, dtype=torch.float32).view(1, 3, 1, 1)
+    resize / centre crop in front of it are identities.  dtype: the arithmetic's type (float64 for the float64 references)."""
+    x = frames_u8.to(dtype) / 255.0
+    mean = torch.tensor(CLIP_MEAN, dtype=dtype).view(1, 3, 1, 1)
+    std = torch.tensor(CLIP_STD, dtype=dtype).view(1, 3, 1, 1)
     return (x - mean) / std
 
 
@@ -46,13 +46,14 @@ def quick_gelu(x):
 
 
 def vit_forward(sd: dict, pixel_values: torch.Tensor, heads: int, prefix: str = "",
-                return_tokens: bool = False, trace: list = None) -> torch.Tensor:
+                return_tokens: bool = False, trace: list = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """pixel_values [F,3,R,R] f32 (already normalised) -> [F,E] f32.
-    trace (optional list): receives (stage name, residual stream [F,N,D]) after ln_pre and after every residual add."""
-    g = lambda k: sd[prefix + k].to(torch.float32)
+    trace (optional list): receives (stage name, residual stream [F,N,D]) after ln_pre and after every residual add.
+    dtype: the arithmetic's type (float64: the float64 references of the tests differentiate through this very graph)."""
+    g = lambda k: sd[prefix + k].to(dtype)
     conv_w = g("conv1.weight")
     D, _, p, _ = conv_w.shape
-    x = F.conv2d(pixel_values.to(torch.float32), conv_w, stride=p)           # [F,D,g,g]
+    x = F.conv2d(pixel_values.to(dtype), conv_w, stride=p)           # [F,D,g,g]
     Fn = x.shape[0]
     x = x.reshape(Fn, D, -1).permute(0, 2, 1)                                 # [F,g*g,D]
     cls = g("class_embedding").view(1, 1, D).expand(Fn, 1, D)
