@@ -902,6 +902,32 @@ size_t vmc_loss_scale_workspace_bytes(size_t n);
 int vmc_loss_scale_check(const float* grad, size_t n, vmc_loss_scale_state* ls, float* hyper, float* clip, void* train_state,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LoRA adapters on a frozen linear (vimo_clip_amd/lora.py) ----------------------------------------------
+ * An adapted linear y = x W^T + s (x A^T) B^T runs the existing GEMM on xcat = [x | ts | 0] and Wcat = [W16 | B16 | 0], both 64
+ * columns wider: the adapter term is one more K tile of the fp32 accumulation.  The two launches that are new:
+ *
+ * vmc_lora_down_concat: for every row m < M
+ *     out[m, 0:K]              = x[m, 0:K]                                      bit for bit, when copy_x != 0 (untouched otherwise)
+ *     out[m, col0 + j]         = round16(scale * sum_k x[m, k] a16[j, k])       j < r; fp32 MFMA accumulation, one 16-bit rounding
+ *     out[m, col0 + r : col0 + 64] = 0
+ * x [M, ldx], a16 [r, lda], out [M, ldo] 16-bit; nothing else of out is written.  x is read once: the fragments that feed the MFMAs
+ * are the registers stored.  HBM: M K 2 B read, M (K + 64) 2 B written.  The backward calls it with x = dz and a16 = B16^T [r, N].
+ * x may be out itself with copy_x == 0 (the first K columns of a concat buffer filled by the caller).
+ * Before any launch -- VMC_E_ARG: a NULL pointer.  VMC_E_SHAPE: M < 1, K % 64 != 0, r % 8 != 0 or outside 8..64, col0 < K,
+ * col0 % 8 != 0, ldx < K, lda < K, ldo < col0 + 64.  VMC_E_ALIGN: a pointer not 16-byte aligned, a leading dimension % 8 != 0. */
+int vmc_lora_down_concat(const void* x, int ldx, const void* a16, int lda, void* out, int ldo, int M, int K, int r, int col0,
+                         float scale, int copy_x, int dtype16, void* stream);
+
+/* vmc_lora_wgrad_tn: out[j, c] = sum_m t[m, j] x[m, c], fp32, overwritten; out is [r, C] contiguous, or [C, r] with
+ * transpose_out != 0.  t [M, ldt] and x [M, ldx] are 16-bit column windows of wider buffers (what lies beyond r / C columns or M rows
+ * is never read).  The tokens are cut into slices whose fp32 slabs are added in slice order: no atomics, the same bits every call.
+ * HBM: about M (C + r) 2 B read.  workspace: vmc_lora_wgrad_tn_workspace_bytes(M, r, C) bytes (0 when one slice suffices),
+ * 16-byte aligned.  Before any launch -- VMC_E_ARG: t / x / out NULL, workspace NULL or too small.  VMC_E_SHAPE: M < 1, r % 8 != 0
+ * or outside 8..64, C % 8 != 0, ldt < r, ldx < C.  VMC_E_ALIGN: a pointer not 16-byte aligned, ldt or ldx % 8 != 0. */
+size_t vmc_lora_wgrad_tn_workspace_bytes(int M, int r, int C);
+int vmc_lora_wgrad_tn(const void* t, int ldt, const void* x, int ldx, float* out, int M, int r, int C, int transpose_out,
+                      void* workspace, size_t workspace_bytes, int dtype16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,11 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
     recompute = getattr(model, "recompute", "none")
     if recompute not in RECOMPUTE_MODES:
         raise ValueError(f"VisionTransformer.recompute must be one of {RECOMPUTE_MODES}, got {recompute!r}")
+    lora = getattr(model, "lora", None)              # lora.add_lora: the blocks' linears carry adapters
+    if lora is not None:
+        if recompute != "none":
+            raise ValueError("LoRA adapters are not supported together with recompute='block'")
+        lora.refresh(dt16)                           # 16-bit copies of the frozen weights and of every adapter (at most one launch)
     F = x.shape[0]
     g = model.input_resolution // model.patch_size
     N = g * g + 1
@@ -44,18 +49,27 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
             xs = _BlockFn.apply(xs, (F, N, H, dt16, model.residual_dtype == torch.float32, cls_only and i + 1 == len(blocks)),
                                 *(blk.get_parameter(name) for name in _BLOCK_PARAMS))
             continue
+        sites = lora.blocks[i] if lora is not None else {}
         h, xs = ag.layernorm(xs, blk.ln_1.weight, blk.ln_1.bias, dt16, passthrough=True)
-        qkv = ag.linear(h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
+        qkv = _linear(sites.get("attn.in_proj"), h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
         o = ag.SelfAttnPackedFn.apply(qkv, None, F, N, H)
         if cls_only and i + 1 == len(blocks):
             o, xs = _ClsRowsFn.apply(o, F, N), _ClsRowsFn.apply(xs, F, N)
-        xs = ag.linear(o, blk.attn.out_proj.weight, blk.attn.out_proj.bias, res=xs,
-                       out_f32=(model.residual_dtype == torch.float32))
+        xs = _linear(sites.get("attn.out_proj"), o, blk.attn.out_proj.weight, blk.attn.out_proj.bias, res=xs,
+                     out_f32=(model.residual_dtype == torch.float32))
         h, xs = ag.layernorm(xs, blk.ln_2.weight, blk.ln_2.bias, dt16, passthrough=True)
-        u = ag.linear(h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=ops.ACT_QUICKGELU)
-        xs = ag.linear(u, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, res=xs,
-                       out_f32=(model.residual_dtype == torch.float32))
+        u = _linear(sites.get("mlp.c_fc"), h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=ops.ACT_QUICKGELU)
+        xs = _linear(sites.get("mlp.c_proj"), u, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, res=xs,
+                     out_f32=(model.residual_dtype == torch.float32))
     return xs, F, N, cls_only
+
+
+def _linear(site, x, weight, bias, **kw):
+    """ag.linear, or the adapted linear of lora.py where the block carries adapters on this weight."""
+    if site is None:
+        return ag.linear(x, weight, bias, **kw)
+    from .lora import lora_linear
+    return lora_linear(site, x, bias, **kw)
 
 
 RECOMPUTE_MODES = ("none", "block")

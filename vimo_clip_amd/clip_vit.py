@@ -173,6 +173,9 @@ class VisionTransformer(nn.Module):
     def _encode_patches(self, patches: torch.Tensor, F: int, trace: list = None, patch_mode: str = "plain") -> torch.Tensor:
         """trace (tests only): receives (stage, copy of the residual stream [F*N, D]) after ln_pre and after each residual add
         of every block but the last MLP add (there only the class rows are formed)."""
+        if getattr(self, "lora", None) is not None:
+            raise RuntimeError("the inference path does not read LoRA adapters: run autograd_vit.vit_forward_train (FlowStudentModel.forward "
+                               "does, also without gradients) or fold them into the weights with lora.merge_lora")
         dt16, D, H = self.compute_dtype, self.width, self.heads
         g = self.input_resolution // self.patch_size
         g2, N = g * g, g * g + 1

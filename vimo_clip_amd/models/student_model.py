@@ -71,10 +71,15 @@ class ResidualMLP(nn.Module):
 
 class FlowStudentModel(nn.Module):
     def __init__(self, clip_model_name="ViT-B/32", device="cuda", num_classes=140, alpha=0.1,
-                 compute_dtype=torch.bfloat16, residual_dtype=torch.float32, recompute="none"):
+                 compute_dtype=torch.bfloat16, residual_dtype=torch.float32,
+                 lora_rank=0, lora_alpha=None, lora_targets=("attn",), recompute="none"):
         """recompute: "none" or "block" (VisionTransformer.recompute: the training forward keeps one stream per block and
-        recomputes the block in the backward pass; same results, a fraction of the activation memory)."""
+        recomputes the block in the backward pass; same results, a fraction of the activation memory).
+        lora_rank > 0: the tower is frozen and rank-r adapters on the `lora_targets` linears of every block are trained with the two
+        heads (lora.add_lora; alpha defaults to 2 rank).  0: no adapters, the model and its ``state_dict`` are what they always were."""
         super().__init__()
+        if lora_rank and recompute != "none":
+            raise ValueError("LoRA adapters are not supported together with recompute='block'")
         self.device = device
         self.compute_dtype = compute_dtype
         self.visual_encoder = VisionTransformer.from_name(clip_model_name, compute_dtype=compute_dtype,
@@ -88,6 +93,9 @@ class FlowStudentModel(nn.Module):
         _init_linear(self.classification_head[0])
         _init_linear(self.classification_head[2])
         self.to(device)
+        if lora_rank:
+            from ..lora import add_lora
+            add_lora(self.visual_encoder, lora_rank, alpha=lora_alpha, targets=lora_targets)
 
     def _frames_u8(self, flow_videos, unit_u8=False):
         """[B,T,C,H,W] -> (u8 frames [B*T,C,H,W] on the device, wrap_quirk): the pixels ``to_pil_image(frame)`` holds (:78), or the
@@ -110,7 +118,9 @@ class FlowStudentModel(nn.Module):
         B, T = flow_videos.shape[:2]
         frames, wrap = self._frames_u8(flow_videos, unit_u8)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if train:
+        # live adapters: the no-grad forward runs the same launches as the training forward (concat + GEMM), so that validation
+        # during training sees them; lora.merge_lora puts the model back on encode_frames_u8
+        if train or getattr(self.visual_encoder, "lora", None) is not None:
             emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=wrap)          # [B*T, E] f32
         else:
             emb = self.visual_encoder.encode_frames_u8(frames, wrap_quirk=wrap)
@@ -146,6 +156,7 @@ class FlowStudentModel(nn.Module):
         rgb = rgb_videos.to(self.device)
         prev = prev.to(self.device) if prev is not None else None
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        train = train or getattr(self.visual_encoder, "lora", None) is not None      # live adapters: through forward, as in training
         ch = 3 if train else 1
         diff = torch.empty((B, n, ch, H, W), dtype=torch.uint8, device=rgb.device)
         for b in range(B):

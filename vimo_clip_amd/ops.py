@@ -479,3 +479,37 @@ def act_bwd(x: torch.Tensor, dy: torch.Tensor, act: int) -> torch.Tensor:
     dx = torch.empty_like(x)
     check(lib.vmc_act_bwd(ptr(x), ptr(dy), ptr(dx), x.numel(), act, dt(x), stream()), "act_bwd")
     return dx
+
+
+LORA_TAIL = 64      # columns the adapter term occupies behind the K columns of a concat buffer
+
+
+def lora_down_concat(x: torch.Tensor, a16: torch.Tensor, r: int, scale: float, out: torch.Tensor = None, copy_x: bool = True,
+                     col0: int = None) -> torch.Tensor:
+    """out [M, K + 64] = [ x | round16(scale * x @ a16[:r]^T) | 0 ] (vmc_lora_down_concat).  x [M, K] 16-bit (row stride free),
+    a16 [>= r, K].  out given with copy_x=False: only the 64 tail columns at col0 (default K) are written."""
+    M, K = x.shape
+    col0 = K if col0 is None else col0
+    if out is None:
+        out = torch.empty((M, col0 + LORA_TAIL), dtype=x.dtype, device=x.device)
+    if x.stride(1) != 1 or a16.stride(1) != 1 or out.stride(1) != 1 or a16.dtype != x.dtype or out.dtype != x.dtype:
+        raise ValueError("lora_down_concat: operands must share one 16-bit dtype and be contiguous in their last dimension")
+    check(lib.vmc_lora_down_concat(ptr(x), x.stride(0), ptr(a16), a16.stride(0), ptr(out), out.stride(0), M, K, int(r), col0, float(scale),
+                                   int(copy_x), dt(x), stream()), "lora_down_concat")
+    return out
+
+
+def lora_wgrad_tn(t: torch.Tensor, x: torch.Tensor, out: torch.Tensor, transpose_out: bool = False) -> torch.Tensor:
+    """out [r, C] (or [C, r] with transpose_out; f32, contiguous, overwritten) = t[M, r]^T @ x[M, C] (vmc_lora_wgrad_tn); t and x may be
+    column windows of wider buffers."""
+    M, r = t.shape
+    C = x.shape[1]
+    if x.shape[0] != M or t.stride(1) != 1 or x.stride(1) != 1 or t.dtype != x.dtype:
+        raise ValueError("lora_wgrad_tn: t and x need the same rows, one 16-bit dtype and unit column stride")
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != r * C:
+        raise ValueError("lora_wgrad_tn: out must be contiguous float32 with r * C elements")
+    nbytes = lib.vmc_lora_wgrad_tn_workspace_bytes(M, r, C)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=t.device) if nbytes else None
+    check(lib.vmc_lora_wgrad_tn(ptr(t), t.stride(0), ptr(x), x.stride(0), ptr(out), M, r, C, int(transpose_out), ptr(ws), nbytes, dt(t),
+                                stream()), "lora_wgrad_tn")
+    return out

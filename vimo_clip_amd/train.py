@@ -97,6 +97,30 @@ def _loss_scale_arg(text):
     return str(text).strip().lower()
 
 
+def lora_kwargs(args) -> dict:
+    """``--lora_rank / --lora_alpha / --lora_targets`` -> FlowStudentModel's keyword arguments; rank 0 (the default): none at all,
+    the model is built exactly as before."""
+    rank = int(getattr(args, "lora_rank", 0) or 0)
+    if rank == 0:
+        return {}
+    targets = getattr(args, "lora_targets", "attn")
+    targets = tuple(t for t in targets.replace("+", ",").split(",") if t) if isinstance(targets, str) else tuple(targets)
+    return {"lora_rank": rank, "lora_alpha": getattr(args, "lora_alpha", None), "lora_targets": targets}
+
+
+def save_best(model, path: str) -> None:
+    """The best-so-far checkpoint.  With live adapters it is written MERGED (lora.merged_state_dict: W + s B A, the reference's keys),
+    so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are."""
+    from .checkpoint import add_prefix, save_state_dict
+    if getattr(model.visual_encoder, "lora", None) is None:
+        return save_state_dict(model, path)
+    import os
+
+    from .lora import merged_state_dict
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    torch.save(add_prefix({k: v.to("cpu") for k, v in merged_state_dict(model).items()}), path)
+
+
 def _class_loss(logits, labels, class_positive_weight, single_label):
     if single_label:                                   # train_frame_diff_mn.py:102
         return cross_entropy_loss(logits, labels.argmax(dim=1))
@@ -143,9 +167,13 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     dtype_name = getattr(args, "compute_dtype", "bf16")
     model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha,
                              recompute=getattr(args, "recompute", "none"),
-                             **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}))
+                             **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}), **lora_kwargs(args))
     arena = GradArena(model.parameters())
     parallel.broadcast_parameters(arena.flat_param)
+    if world > 1:                                          # a frozen tower (LoRA) is outside the arena: it starts from rank 0's too
+        for p in model.parameters():
+            if not p.requires_grad:
+                parallel.broadcast_parameters(p.data)
     optimizer = FusedAdam(arena, lr=args.learning_rate)
     reducer = parallel.GradientAllReducer(arena.flat_grad).attach(arena)     # buckets go out during the backward
     clip_norm = None if single else args.grad_clip_norm
@@ -196,7 +224,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
             from .checkpoint import save_state_dict
             save_state_dict(model, f"{ckpt_dir}/student_epoch_{epoch + 1}.pth")
             if vt < best:
-                save_state_dict(model, f"{ckpt_dir} - best/student_best.pth")
+                save_best(model, f"{ckpt_dir} - best/student_best.pth")
         best = min(best, vt)
         if rank == 0:
             line = {"epoch": epoch + 1, "val_distill": vd, "val_class": vc, "val_total": vt,
@@ -234,6 +262,12 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--loss_scale", default="off", type=_loss_scale_arg, metavar="{off,dynamic,<number>}",
                    help="loss scaling for float16 gradients, on the device: dynamic = GradScaler's defaults; a number = a static "
                         "scale; an overflowing step is skipped either way")
+    # absent unless given (lora_kwargs reads them with defaults): the namespace of a run without adapters is the one it always was
+    p.add_argument("--lora_rank", type=int, default=argparse.SUPPRESS,
+                   help="parameter-efficient fine-tuning: freeze the tower and train rank-r adapters (a multiple of 8, at most 64) plus "
+                        "the two heads; default 0 = full fine-tuning, the loop as it was")
+    p.add_argument("--lora_alpha", type=float, default=argparse.SUPPRESS, help="adapter scale numerator (s = alpha / rank); default 2 rank")
+    p.add_argument("--lora_targets", default=argparse.SUPPRESS, help="attn (default), mlp or attn+mlp: which linears of every block carry adapters")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

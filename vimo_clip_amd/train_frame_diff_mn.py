@@ -40,6 +40,9 @@ def build_parser() -> argparse.ArgumentParser:
     arg("compute_dtype", default="bf16", choices=["bf16", "f16"], help="16-bit type of the GEMM and attention operands")
     arg("loss_scale", default="off", metavar="{off,dynamic,<number>}",
         help="loss scaling for float16 gradients, on the device (train.parse_loss_scale): dynamic, or a number for a static scale")
+    arg("lora_rank", type=int, default=0, help="train rank-r LoRA adapters and the heads on a frozen tower (train.lora_kwargs); 0 = off")
+    arg("lora_alpha", type=float, default=None, help="adapter scale numerator (s = alpha / rank); default 2 rank")
+    arg("lora_targets", default="attn", help="attn, mlp or attn+mlp")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
