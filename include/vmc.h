@@ -701,8 +701,9 @@ int vmc_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
  *          (with gradient clipping vmc_grad_clip_dev writes [3], with loss scaling vmc_loss_scale_check does: both below)
  * vmc_train_tick: t += 1, recomputes hyper[1..2] and the n_seeds seeds (splitmix of base seed, t and the index); enqueue it once
  * per step before the forward.  vmc_adam_step_dev = vmc_adam_step reading its four scalars from `hyper`.
- * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd): a value < 2^63 is the seed itself; with bit
- * 63 set the low 63 bits are the ADDRESS of a u64 in device memory holding it (e.g. &state[2 + i]), read at kernel start.
+ * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd, vmc_patch_keep_sample): a value < 2^63 is the
+ * seed itself; with bit 63 set the low 63 bits are the ADDRESS of a u64 in device memory holding it (e.g. &state[2 + i]), read at
+ * kernel start.
  * POOL LENGTH (the `_len` entries: vmc_mean_pool_len / _bwd_len, vmc_tfam_head_fwd_len, vmc_tfam_forward_len,
  * vmc_tfam_head_train_fwd_len, vmc_tfam_head_bwd_len, vmc_tfam_train_fwd_len / _bwd_len): the same idea for the mean-pool.
  * `pool_len` points to ONE int32 in DEVICE memory, n = the number of leading rows of every clip that enter the mean, read at
@@ -927,6 +928,44 @@ int vmc_lora_down_concat(const void* x, int ldx, const void* a16, int lda, void*
 size_t vmc_lora_wgrad_tn_workspace_bytes(int M, int r, int C);
 int vmc_lora_wgrad_tn(const void* t, int ldt, const void* x, int ldx, float* out, int M, int r, int C, int transpose_out,
                       void* workspace, size_t workspace_bytes, int dtype16, void* stream);
+
+/* ---- Patch dropout in the student's training stem (vimo_clip_amd/autograd_vit.py) -------------------------------
+ * Per frame the class token and Kp of the G = g^2 patch tokens are kept; the tower then runs on Kp + 1 tokens per frame.  Four
+ * memory-bound launches, 16-byte accesses where the rows allow, no floating-point atomics: the same bits every call.
+ *
+ * vmc_patch_keep_sample: keep[f, 0:Kp] = the Kp patches of frame f with the smallest (key, n), key = hash32(seed, f G + n) (the
+ * counter hash of vmc_dropout), written in ascending n.  (key, n) is a strict total order, so the set is one definite subset.  seed:
+ * see "SEED ARGUMENTS" (a value, or with bit 63 set the device address of one).  keep int32 [F, Kp].  One workgroup per frame.
+ * VMC_E_ARG: keep NULL, F < 1.  VMC_E_SHAPE: not 1 <= Kp <= G <= 1024. */
+int vmc_patch_keep_sample(uint64_t seed, int F, int G, int Kp, int* keep, void* stream);
+
+/* vmc_gather_rows16: dst[f Kp + j, 0:cols] = src[f G + idx[f, j], 0:cols], bit copies of 16-bit rows (the patch matrix of any of the
+ * patch entry points: cols = kpad, 2 kpad or 3 kpad).  ld_src, ld_dst: row strides in elements.  An id outside 0..G-1 is clamped into
+ * it.  HBM: F Kp cols 2 B read and written.  VMC_E_ARG: a NULL pointer, F < 1, cols < 1.  VMC_E_SHAPE: not 1 <= Kp <= G, a stride
+ * below cols.  Rows that are not 16-byte aligned (cols or a stride % 8 != 0, a pointer) are copied element by element. */
+int vmc_gather_rows16(const void* src, int ld_src, const int* idx, int G, void* dst, int ld_dst, int cols, int F, int Kp,
+                      void* stream);
+
+/* vmc_assemble_tokens_keep: vmc_assemble_tokens on the kept patches, N' = Kp + 1 tokens per frame:
+ *     x[f N', :] = cls + pos[0];   x[f N' + 1 + j, :] = xp[f Kp + j, :] + pos[keep[f, j] + 1, :]
+ * one fp32 add and the store rounding of x's type, as vmc_assemble_tokens.  xp 16-bit [F Kp, D]; cls f32 [D]; pos f32 [G + 1, D];
+ * keep int32 [F, Kp] (ids outside 0..G-1 are clamped); x [F N', D] f32 or the 16-bit type.  HBM: F Kp D 2 B read, F N' D x B written;
+ * the positional table is read through the caches.
+ * VMC_E_ARG: a NULL pointer, F < 1, D < 1.  VMC_E_SHAPE: not 1 <= Kp <= G.  VMC_E_DTYPE: x neither f32 nor dtype16. */
+int vmc_assemble_tokens_keep(const void* xp, const float* cls, const float* pos, const int* keep, void* x, int F, int G, int Kp,
+                             int D, int x_dtype, int dtype16, void* stream);
+
+/* vmc_assemble_tokens_keep_bwd: dx [F N', D] f32 or 16-bit ->
+ *     dxp16[f Kp + j, :] = round16(dx[f N' + 1 + j, :])
+ *     dpos[0, :] = dcls = sum_f dx[f N', :];   dpos[n + 1, :] = sum over the frames f that kept patch n of dx[f N' + 1 + slot_f(n), :]
+ * (exact zeros where no frame kept n; every row of dpos [G + 1, D] is written).  fp32 sums over the frames in ascending order, cut
+ * into at most 8 slabs of frames whose partial sums are added in slab order: the order depends on (F, keep) only.
+ * workspace: vmc_assemble_tokens_keep_bwd_workspace_bytes(F, G, D) bytes, 16-byte aligned (the inverse of keep, and the slabs).
+ * HBM: F N' D dx read twice, F Kp D 2 B written.  VMC_E_ARG: a NULL pointer, F < 1, D < 1, workspace too small.  VMC_E_SHAPE: not
+ * 1 <= Kp <= G.  VMC_E_ALIGN: workspace.  VMC_E_DTYPE: dx neither f32 nor dtype16. */
+size_t vmc_assemble_tokens_keep_bwd_workspace_bytes(int F, int G, int D);
+int vmc_assemble_tokens_keep_bwd(const void* dx, const int* keep, void* dxp16, float* dcls, float* dpos, int F, int G, int Kp, int D,
+                                 int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

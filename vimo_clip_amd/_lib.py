@@ -137,6 +137,11 @@ SIGNATURES = {
     "vmc_lora_down_concat": (I, [P, I, P, I, P, I, I, I, I, I, F, I, I, P]),
     "vmc_lora_wgrad_tn_workspace_bytes": (Z, [I, I, I]),
     "vmc_lora_wgrad_tn": (I, [P, I, P, I, P, I, I, I, I, P, Z, I, P]),
+    "vmc_patch_keep_sample": (I, [ctypes.c_uint64, I, I, I, P, P]),
+    "vmc_gather_rows16": (I, [P, I, P, I, P, I, I, I, I, P]),
+    "vmc_assemble_tokens_keep": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
+    "vmc_assemble_tokens_keep_bwd_workspace_bytes": (Z, [I, I, I]),
+    "vmc_assemble_tokens_keep_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, P, Z, P]),
 }
 
 

@@ -685,6 +685,26 @@ class AssembleTokensFn(torch.autograd.Function):
         return dxp, _deliver(ctx.cls, dcls), _deliver(ctx.pos, dpos), None, None, None
 
 
+class AssembleTokensKeepFn(torch.autograd.Function):
+    """AssembleTokensFn under patch dropout: xp holds the Kp kept patch rows of every frame, keep [F, Kp] int32 their patch ids
+    (ascending); the token matrix is [F*(Kp+1), D] and the positional embedding is gathered per frame.  The backward scatters the
+    positional gradient back (exact zeros where no frame kept a position), with sums in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, xp, cls, pos, keep, out_dtype):
+        x = ops.assemble_tokens_keep(xp, cls.detach(), pos.detach(), keep, out_dtype)
+        ctx.cls, ctx.pos, ctx.keep, ctx.dt16 = cls, pos, keep, xp.dtype
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        cls, pos = ctx.cls, ctx.pos
+        G, D = pos.shape[0] - 1, pos.shape[1]
+        dxp, dcls, dpos = ops.assemble_tokens_keep_bwd(dx.contiguous(), ctx.keep, G, ctx.dt16,
+                                                       dcls=_grad_out(cls, (D,)), dpos=_grad_out(pos, (G + 1, D)))
+        return dxp, _deliver(cls, dcls), _deliver(pos, dpos), None, None
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):

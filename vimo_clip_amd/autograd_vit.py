@@ -6,17 +6,47 @@ kept in the compute dtype; the residual stream uses ``model.residual_dtype``.
 
 ``model.recompute = "block"`` keeps only the input stream of every residual block for the backward pass and recomputes the block
 there (_BlockFn); ``saved_activation_bytes`` counts what either mode keeps.
+
+``model.patch_dropout = p > 0`` (training with gradients only) keeps the class token and Kp = max(1, int(g^2 (1 - p))) randomly drawn
+patch tokens of every frame: the patch GEMM, the tower and their backward run on Kp + 1 rows per frame (``patch_keep_for``).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import autograd_ops as ag
-from . import ops
+from . import ops, synth
 
 
-def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only: bool = True):
+def _mix64(x: int) -> int:
+    """synth._mix64 (the splitmix64 finaliser) on one Python int."""
+    return int(synth._mix64(np.array([x & 0xFFFFFFFFFFFFFFFF], dtype=np.uint64))[0])
+
+
+def patch_keep_for(model, F: int, device):
+    """The keep set [F, Kp] int32 of this training forward, or None when nothing is dropped: ``model.patch_dropout`` is 0, the model
+    is in eval mode, or no gradient is being recorded.  The seed is ``model.patch_dropout_seed_address`` verbatim when set (a device
+    address with bit 63, e.g. FusedAdam.seed_address(i): a captured step then draws anew on every replay); otherwise the splitmix
+    finaliser of ``model.patch_dropout_seed`` and the number of sets this model has drawn so far."""
+    p = float(getattr(model, "patch_dropout", 0.0) or 0.0)
+    if p <= 0.0 or not model.training or not torch.is_grad_enabled():
+        return None
+    if not p < 1.0:
+        raise ValueError(f"VisionTransformer.patch_dropout must be in [0, 1), got {p}")
+    g = model.input_resolution // model.patch_size
+    seed = getattr(model, "patch_dropout_seed_address", None)
+    if seed is None:
+        calls = getattr(model, "_patch_dropout_calls", 0)
+        model._patch_dropout_calls = calls + 1
+        seed = _mix64(_mix64(int(getattr(model, "patch_dropout_seed", 0))) + calls) >> 1          # a value below 2^63
+    return ops.patch_keep_sample(seed, F, g * g, ops.patch_keep_count(g * g, p), device)
+
+
+def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only: bool = True, keep: torch.Tensor = None):
     """x: u8 [F,3,R,R] frames or float pixel values.  Returns (the final residual stream, F, N, rows_are_cls).
+    keep: int32 [F, Kp] device tensor of ascending patch ids per frame: only those patches (and the class token) enter the tower and
+    the N returned is Kp + 1; None: ``patch_keep_for(model)`` decides (nothing is dropped unless ``model.patch_dropout`` asks for it).
     cls_only: only x[:, 0] of the last block reaches ln_post, so its out_proj / ln_2 / MLP run on the F class rows (forward and,
     through autograd, backward: the dgrad / wgrad GEMMs of those four linears shrink by N as well); the stream returned is then
     [F, D].  The attention of the last block still sees every token (its K / V gradients flow to all rows)."""
@@ -32,14 +62,22 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
     F = x.shape[0]
     g = model.input_resolution // model.patch_size
     N = g * g + 1
+    if keep is None:
+        keep = patch_keep_for(model, F, model.class_embedding.device)
     with torch.no_grad():   # the input frames carry no gradient
         if x.dtype == torch.uint8:
             x, wrap_quirk = model.fit_frames_u8(x, wrap_quirk)
             patches = ops.preprocess_patches_u8(x, model.patch_size, dt16, wrap_quirk)
         else:
             patches = ops.patches_f32(x, model.patch_size, dt16)
-    xp = ag.linear(patches, model.conv1.weight)                                    # [F*g*g, D]
-    xs = ag.AssembleTokensFn.apply(xp, model.class_embedding, model.positional_embedding, F, N, model.residual_dtype)
+        if keep is not None:                                                       # patch dropout: the GEMM sees the kept rows only
+            patches = ops.gather_rows16(patches, keep, g * g)
+            N = keep.shape[1] + 1
+    xp = ag.linear(patches, model.conv1.weight)                                    # [F*g*g, D], or [F*Kp, D]
+    if keep is None:
+        xs = ag.AssembleTokensFn.apply(xp, model.class_embedding, model.positional_embedding, F, N, model.residual_dtype)
+    else:
+        xs = ag.AssembleTokensKeepFn.apply(xp, model.class_embedding, model.positional_embedding, keep, model.residual_dtype)
     xs = ag.layernorm(xs, model.ln_pre.weight, model.ln_pre.bias, dt16, out_f32=(model.residual_dtype == torch.float32))
     if model.residual_dtype != torch.float32:
         xs = ag.cast(xs, model.residual_dtype)
@@ -147,7 +185,7 @@ class _BlockFn(torch.autograd.Function):
 
 
 def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes16: int = 2, residual_bytes: int = 4,
-                           cls_only: bool = True) -> int:
+                           cls_only: bool = True, tokens: int = None) -> int:
     """Bytes the residual blocks of the training forward keep for the backward pass (what the per-op Functions of autograd_ops
     hand to ``save_for_backward``; the patch GEMM, ln_pre, ln_post and the projection are not counted).
     geometry: a model name or (resolution, patch, width, layers, heads, output_dim).
@@ -155,7 +193,8 @@ def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes
     the c_fc pre-activation and the QuickGELU output -- (2 r + 14 b) D bytes (36 D for fp32 / 16-bit) -- plus lse (4 H) and two
     (mean, rstd) pairs (16).  With cls_only the last block keeps everything after its attention for the F class rows only.
     "block": one input stream per block, r D bytes per row.  During the backward one recomputed block ("none" with one layer, the
-    last block's class-row shortcut aside) is alive on top of that."""
+    last block's class-row shortcut aside) is alive on top of that.
+    tokens: token rows per frame instead of the geometry's g^2 + 1 (patch dropout: Kp + 1)."""
     if recompute not in RECOMPUTE_MODES:
         raise ValueError(f"recompute must be one of {RECOMPUTE_MODES}, got {recompute!r}")
     if isinstance(geometry, str):
@@ -163,6 +202,10 @@ def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes
         geometry = vit_geometry(geometry)
     R, p, D, L, H, _E = geometry
     N = (R // p) ** 2 + 1
+    if tokens is not None:
+        if not 2 <= tokens <= N:
+            raise ValueError(f"tokens must be in 2..{N} for this geometry, got {tokens}")
+        N = tokens
     rows, r, b = frames * N, residual_bytes, bytes16
     if recompute == "block":
         return L * rows * r * D
@@ -230,9 +273,9 @@ class _ProjFn(torch.autograd.Function):
         return dx, ag._deliver(proj, out)
 
 
-def vit_forward_train(model, x: torch.Tensor, wrap_quirk: bool = False) -> torch.Tensor:
-    """[F,3,R,R] -> [F,E] f32 embeddings, differentiable w.r.t. every ViT parameter."""
-    xs, F, N, rows_are_cls = vit_tokens_train(model, x, wrap_quirk, cls_only=getattr(model, "cls_only_last_block", True))
+def vit_forward_train(model, x: torch.Tensor, wrap_quirk: bool = False, keep: torch.Tensor = None) -> torch.Tensor:
+    """[F,3,R,R] -> [F,E] f32 embeddings, differentiable w.r.t. every ViT parameter.  keep: see vit_tokens_train."""
+    xs, F, N, rows_are_cls = vit_tokens_train(model, x, wrap_quirk, cls_only=getattr(model, "cls_only_last_block", True), keep=keep)
     cls = xs if rows_are_cls else _ClsRowsFn.apply(xs, F, N)
     h = ag.layernorm(cls, model.ln_post.weight, model.ln_post.bias, model.compute_dtype)
     return _ProjFn.apply(h, model.proj)

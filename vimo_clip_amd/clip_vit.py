@@ -103,6 +103,11 @@ class VisionTransformer(nn.Module):
         # training forward: "block" saves one input stream per residual block and recomputes the block in the backward pass
         # (autograd_vit._BlockFn: same bits, 4 D instead of 36 D bytes per token row and block); "none" saves every intermediate
         self.recompute = "none"
+        # training forward with gradients, train() mode: keep the class token and max(1, int(g^2 (1 - p))) random patch tokens per frame
+        # (autograd_vit.patch_keep_for; open_clip's PatchDropout).  0: every token, and none of the patch-dropout launches
+        self.patch_dropout = 0.0
+        self.patch_dropout_seed = 0              # base of the keep-set stream (mixed with a per-model call counter) ...
+        self.patch_dropout_seed_address = None   # ... or a seed argument in device-address form, used as it is
         self.frame_chunk = 256  # frames per pass (bounds activation memory; F*N*4D*2 B for the MLP buffer)
         self._init_weights()
 

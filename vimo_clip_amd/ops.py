@@ -513,3 +513,71 @@ def lora_wgrad_tn(t: torch.Tensor, x: torch.Tensor, out: torch.Tensor, transpose
     check(lib.vmc_lora_wgrad_tn(ptr(t), t.stride(0), ptr(x), x.stride(0), ptr(out), M, r, C, int(transpose_out), ptr(ws), nbytes, dt(t),
                                 stream()), "lora_wgrad_tn")
     return out
+
+
+# ---- patch dropout in the student's training stem (include/vmc.h) --------------------------------------------------
+PATCH_KEEP_MAX_G = 1024
+
+
+def patch_keep_count(patches_per_frame: int, p: float) -> int:
+    """Kp = max(1, int(G (1 - p))): open_clip's PatchDropout rule."""
+    return max(1, int(patches_per_frame * (1.0 - p)))
+
+
+def _check_keep(keep: torch.Tensor, F: int, G: int) -> int:
+    if keep.dtype != torch.int32 or keep.dim() != 2 or keep.shape[0] != F or not keep.is_contiguous():
+        raise ValueError(f"keep must be a contiguous int32 [F, Kp] tensor with F = {F}, got {keep.dtype} {tuple(keep.shape)}")
+    Kp = keep.shape[1]
+    if not 1 <= Kp <= G:
+        raise ValueError(f"keep holds {Kp} patches per frame, the frames have {G}")
+    return Kp
+
+
+def patch_keep_sample(seed: int, F: int, G: int, Kp: int, device) -> torch.Tensor:
+    """int32 [F, Kp]: per frame the Kp of G patches with the smallest (hash32(seed, f G + n), n), ascending (vmc_patch_keep_sample).
+    seed: a value below 2^63 or a device address with bit 63 set (FusedAdam.seed_address)."""
+    keep = torch.empty((F, Kp), dtype=torch.int32, device=device)
+    check(lib.vmc_patch_keep_sample(int(seed), F, G, Kp, ptr(keep), stream()), "patch_keep_sample")
+    return keep
+
+
+def gather_rows16(src: torch.Tensor, keep: torch.Tensor, G: int) -> torch.Tensor:
+    """src 16-bit [F*G, cols] (row stride free) -> [F*Kp, cols], row f Kp + j = src row f G + keep[f, j] (vmc_gather_rows16)."""
+    F = src.shape[0] // G
+    Kp = _check_keep(keep, F, G)
+    if src.dim() != 2 or src.shape[0] != F * G or src.stride(1) != 1 or src.element_size() != 2:
+        raise ValueError("gather_rows16: src must be a 16-bit [F*G, cols] matrix with unit column stride")
+    cols = src.shape[1]
+    dst = torch.empty((F * Kp, cols), dtype=src.dtype, device=src.device)
+    check(lib.vmc_gather_rows16(ptr(src), src.stride(0), ptr(keep), G, ptr(dst), cols, cols, F, Kp, stream()), "gather_rows16")
+    return dst
+
+
+def assemble_tokens_keep(xp: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, keep: torch.Tensor, out_dtype) -> torch.Tensor:
+    """[F*(Kp+1), D]: per frame cls + pos[0], then xp[f Kp + j] + pos[keep[f, j] + 1] (vmc_assemble_tokens_keep)."""
+    F, G, D = keep.shape[0], pos.shape[0] - 1, xp.shape[1]
+    Kp = _check_keep(keep, F, G)
+    if xp.shape[0] != F * Kp or not xp.is_contiguous() or pos.shape[1] != D or cls.numel() != D:
+        raise ValueError("assemble_tokens_keep: xp must be contiguous [F*Kp, D], cls [D], pos [G+1, D]")
+    x = torch.empty((F * (Kp + 1), D), dtype=out_dtype, device=xp.device)
+    check(lib.vmc_assemble_tokens_keep(ptr(xp), ptr(cls), ptr(pos), ptr(keep), ptr(x), F, G, Kp, D, dt(x), dt(xp), stream()),
+          "assemble_tokens_keep")
+    return x
+
+
+def assemble_tokens_keep_bwd(dx: torch.Tensor, keep: torch.Tensor, G: int, dtype16, dcls: torch.Tensor = None, dpos: torch.Tensor = None):
+    """dx [F*(Kp+1), D] -> (dxp 16-bit [F*Kp, D], dcls f32 [D], dpos f32 [G+1, D]) (vmc_assemble_tokens_keep_bwd).  dcls / dpos given:
+    contiguous f32 destinations (gradient arena slots), overwritten."""
+    F = keep.shape[0]
+    Kp = _check_keep(keep, F, G)
+    D = dx.shape[1]
+    if dx.shape[0] != F * (Kp + 1) or not dx.is_contiguous():
+        raise ValueError("assemble_tokens_keep_bwd: dx must be contiguous [F*(Kp+1), D]")
+    dxp = torch.empty((F * Kp, D), dtype=dtype16, device=dx.device)
+    dcls = torch.empty(D, dtype=torch.float32, device=dx.device) if dcls is None else dcls
+    dpos = torch.empty((G + 1, D), dtype=torch.float32, device=dx.device) if dpos is None else dpos
+    nbytes = lib.vmc_assemble_tokens_keep_bwd_workspace_bytes(F, G, D)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dx.device)
+    check(lib.vmc_assemble_tokens_keep_bwd(ptr(dx), ptr(keep), ptr(dxp), ptr(dcls), ptr(dpos), F, G, Kp, D, dt(dx), dt(dtype16), ptr(ws),
+                                           nbytes, stream()), "assemble_tokens_keep_bwd")
+    return dxp, dcls, dpos

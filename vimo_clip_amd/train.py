@@ -108,6 +108,29 @@ def lora_kwargs(args) -> dict:
     return {"lora_rank": rank, "lora_alpha": getattr(args, "lora_alpha", None), "lora_targets": targets}
 
 
+def _patch_dropout_arg(text):
+    """``--patch_dropout`` values: a drop fraction 0 <= p < 1."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--patch_dropout needs a number, got {text!r}") from None
+    if not 0.0 <= p < 1.0:
+        raise argparse.ArgumentTypeError(f"--patch_dropout must satisfy 0 <= p < 1, got {text!r}")
+    return p
+
+
+PATCH_DROPOUT_SEED = 0x5EED0D07      # base of the keep-set streams of a training run; rank r draws from base + r
+
+
+def patch_dropout_kwargs(args, rank: int = 0) -> dict:
+    """``--patch_dropout P`` -> FlowStudentModel's keyword arguments; 0 (the default): none at all, the model is built exactly as before.
+    Every data-parallel rank draws from a stream of its own (the seed base is offset by the rank): ranks see different frames."""
+    p = float(getattr(args, "patch_dropout", 0.0) or 0.0)
+    if p == 0.0:
+        return {}
+    return {"patch_dropout": p, "patch_dropout_seed": PATCH_DROPOUT_SEED + int(rank)}
+
+
 def save_best(model, path: str) -> None:
     """The best-so-far checkpoint.  With live adapters it is written MERGED (lora.merged_state_dict: W + s B A, the reference's keys),
     so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are."""
@@ -167,7 +190,8 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     dtype_name = getattr(args, "compute_dtype", "bf16")
     model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha,
                              recompute=getattr(args, "recompute", "none"),
-                             **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}), **lora_kwargs(args))
+                             **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}), **lora_kwargs(args),
+                             **patch_dropout_kwargs(args, rank))
     arena = GradArena(model.parameters())
     parallel.broadcast_parameters(arena.flat_param)
     if world > 1:                                          # a frozen tower (LoRA) is outside the arena: it starts from rank 0's too
@@ -268,6 +292,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "the two heads; default 0 = full fine-tuning, the loop as it was")
     p.add_argument("--lora_alpha", type=float, default=argparse.SUPPRESS, help="adapter scale numerator (s = alpha / rank); default 2 rank")
     p.add_argument("--lora_targets", default=argparse.SUPPRESS, help="attn (default), mlp or attn+mlp: which linears of every block carry adapters")
+    p.add_argument("--patch_dropout", type=_patch_dropout_arg, default=argparse.SUPPRESS, metavar="P",
+                   help="training only: every frame keeps its class token and max(1, int(g^2 (1 - P))) randomly drawn patch tokens, the "
+                        "tower runs on those rows; evaluation sees every token; default 0 = nothing is dropped")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

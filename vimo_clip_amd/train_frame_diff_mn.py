@@ -43,6 +43,9 @@ def build_parser() -> argparse.ArgumentParser:
     arg("lora_rank", type=int, default=0, help="train rank-r LoRA adapters and the heads on a frozen tower (train.lora_kwargs); 0 = off")
     arg("lora_alpha", type=float, default=None, help="adapter scale numerator (s = alpha / rank); default 2 rank")
     arg("lora_targets", default="attn", help="attn, mlp or attn+mlp")
+    arg("patch_dropout", type=float, default=0.0, metavar="P",
+        help="training only: keep the class token and max(1, int(g^2 (1 - P))) random patch tokens per frame (train.patch_dropout_kwargs); "
+             "0 = off")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
@@ -50,6 +53,8 @@ def build_parser() -> argparse.ArgumentParser:
 def train(args):
     from . import train as student_train
     student_train.parse_loss_scale(args.loss_scale)         # a malformed value fails before any file is opened
+    if not 0.0 <= args.patch_dropout < 1.0:
+        raise ValueError(f"--patch_dropout must satisfy 0 <= p < 1, got {args.patch_dropout}")
     size = tuple(args.spatial_size)
     sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
                                   raw_u8=args.device_resize) for path in (args.train_hdf5_path, args.val_hdf5_path))
