@@ -3,7 +3,7 @@
  *
  * The reference (MarcosRodrigoT/VIMO-CLIP) has no FFI: its hot path sits behind Python nn.Module /
  * function signatures and runs on stock PyTorch ATen ops.  Each entry point below replaces the ATen
- * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17..K20 are this project's own).
+ * op site(s) named in its comment (paths relative to the reference checkout; SURVEY.md §2b ids K0..K16; K17..K22 are this project's own).
  * The Python mirror of the reference interface (vimo_clip_amd/) calls these through ctypes.
  *
  * Conventions
@@ -902,6 +902,31 @@ typedef struct vmc_loss_scale_state {
 size_t vmc_loss_scale_workspace_bytes(size_t n);
 int vmc_loss_scale_check(const float* grad, size_t n, vmc_loss_scale_state* ls, float* hyper, float* clip, void* train_state,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K22 — exponential moving average of the trained weights on the flat parameter arena (optim.FusedAdam.enable_ema; DESIGN.md
+ * 3.3.6).  One streaming launch after the optimiser's:
+ *   ema[i] = fmaf(w, p[i] - ema[i], ema[i])          torch.lerp(ema, p, w): one fp32 subtraction, one fused multiply-add
+ *   w = one_minus_decay                               warmup == 0
+ *   w = max(one_minus_decay, 9.0f / (float)(10 + t))  warmup == 1: decay_t = min(decay, (1 + t) / (10 + t)) without the cancellation
+ * one_minus_decay is 1 - decay ROUNDED BY THE HOST from float64: for decay = 0.9999 an fp32 subtraction on the device would be wrong
+ * by about 6e-4 relative.  t is `step` when train_state is NULL; otherwise state[0] of vmc_train_tick (a 64-bit count in device
+ * memory, read by the kernel: a captured step replays with the right weight) and `step` is only range-checked.  skip: device
+ * pointer to one int32 (the found_inf word of vmc_loss_scale_state) or NULL; when *skip != 0 every workgroup returns before its
+ * first store and ema keeps its bytes -- the contract of vmc_adam_step_dev_skip.  ema, p: n fp32 each, 16-BYTE ALIGNED, not
+ * overlapping; any n (the n % 4 tail is done element by element).  inf and NaN propagate.  HBM: 12 B per element.  One launch,
+ * plain vector stores, no LDS, no atomics: the same bits on every call and every replay.  Only enqueues; safe under capture.
+ * Checked in this order, before any launch: ema or p NULL, one_minus_decay outside [0, 1] or NaN, warmup not 0 / 1, step < 0 ->
+ * VMC_E_ARG; ema or p not 16-byte aligned, train_state not 8-byte aligned, skip not 4-byte aligned -> VMC_E_ALIGN; n == 0 ->
+ * success, nothing launched. */
+int vmc_ema_update(float* ema, const float* p, size_t n, float one_minus_decay, int warmup, long long step, const void* train_state,
+                   const int* skip, void* stream);
+
+/* vmc_ema_swap: a[i] <-> b[i] for i < n, bit for bit (NaN payloads, -0 and subnormals included): evaluating with the average needs
+ * no third arena-sized buffer.  A thread loads both values before it stores either.  HBM: 16 B per element.  Only enqueues.
+ * In this order: a or b NULL, a == b, overlapping ranges -> VMC_E_ARG; a or b not 16-byte aligned -> VMC_E_ALIGN; n == 0 ->
+ * success, nothing launched. */
+int vmc_ema_swap(float* a, float* b, size_t n, void* stream);
 
 /* ---- LoRA adapters on a frozen linear (vimo_clip_amd/lora.py) ----------------------------------------------
  * An adapted linear y = x W^T + s (x A^T) B^T runs the existing GEMM on xcat = [x | ts | 0] and Wcat = [W16 | B16 | 0], both 64

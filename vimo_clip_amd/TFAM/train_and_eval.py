@@ -8,6 +8,7 @@ scalars are printed.  Kept quirks: AdamW lr is 1e-4 whatever the config says (:5
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import time
 
@@ -42,6 +43,7 @@ class Config:
         self.device_store = False  # hold both sets in device memory and assemble batches there (data.device_store.DeviceClipStore)
         self.device_metrics = False  # log logits / labels / loss on the device inside the step, read once per epoch (metrics.DeviceMetricLog)
         self.loss_scale = "off"    # "off" | "dynamic" | a number: loss scaling on the device for float16 gradients (optim.FusedAdam.enable_loss_scaling)
+        self.ema_decay = None      # a decay 0 < D < 1: validate and checkpoint an exponential moving average of the weights (optim.FusedAdam.enable_ema); None: off
         self.fused_feature_training = False  # the feature concatenation (concat_dim = -1) trains on the fused chains too (AMO_CLIP.fused_feature_training)
         self.class_names_dir = self.train_dataset_path = self.val_dataset_path = self.frame_diff_dataset_path = None
         self.__dict__.update(kw)
@@ -82,6 +84,8 @@ class Config:
             kw["fused_feature_training"] = bool(t["fused_feature_training"])
         if t.get("loss_scale") is not None:         # optional as well: off | dynamic | a number (YAML reads `off` as False)
             kw["loss_scale"] = "off" if t["loss_scale"] is False else str(t["loss_scale"])
+        if t.get("ema_decay") is not None:          # optional as well: a decay 0 < D < 1
+            kw["ema_decay"] = float(t["ema_decay"])
         kw.update(overrides)
         return cls(**kw)
 
@@ -327,6 +331,9 @@ class ModelTrainer:
             # than the overlap returns; profiles/README.md), so it is opt-in
             self.optimizer.enable_backward_overlap(model.parameter_groups_by_layer())
             model.grad_group_callback = self.optimizer.group_ready
+        if getattr(config, "ema_decay", None) is not None:
+            # the average follows every step on the device, captured or not; validation and the checkpoint's "state_dict" use it
+            self.optimizer.enable_ema(float(config.ema_decay))
 
     def _epoch_rows(self, n_items):
         """Rows this rank logs in one epoch over ``n_items`` videos: its shard (parallel.shard_range), whole batches only."""
@@ -505,7 +512,16 @@ class ModelTrainer:
         stats = parallel.all_reduce_scalars(torch.stack([total, torch.tensor(float(n), device=total.device)]))
         return float(stats[0] / stats[1].clamp(min=1)), float(self.mAP_metric.compute(distributed=self.world > 1))
 
+    def _averaged(self):
+        """``FusedAdam.ema_weights()`` when the weight average is on (``Config.ema_decay``), else a context that does nothing."""
+        return self.optimizer.ema_weights() if getattr(self.optimizer, "ema", None) is not None else contextlib.nullcontext()
+
     def validate(self, epoch):
+        """With ``Config.ema_decay`` the whole pass -- eager, captured or from the device store -- runs on the averaged weights."""
+        with self._averaged():
+            return self._validate(epoch)
+
+    def _validate(self, epoch):
         self.model.eval()
         self.mAP_metric.reset()
         total, n = torch.zeros((), device=self.config.device), 0
@@ -532,7 +548,9 @@ class ModelTrainer:
     def save_checkpoint(self, val_loss, val_mAP, epoch, best=False, path=None):
         """:133-148: the checkpoint dict is written as ``<checkpoint_dir>/best_model.pth`` only when the validation mAP improves
         (rank 0; ``checkpoint_dir = None`` keeps it in memory only).  Tensors are cloned: ``state_dict()`` returns views into
-        the gradient arena, and optimiser moments are live buffers."""
+        the gradient arena, and optimiser moments are live buffers.  With ``Config.ema_decay``, ``"state_dict"`` holds the AVERAGED
+        weights -- what was validated and what ``ModelTester.load_best_model`` reads -- the live ones go in as ``"live_state_dict"``
+        and the optimiser dict carries the average (``"ema"``), so a run can be resumed."""
         from ..checkpoint import snapshot
         improved = val_mAP > self.best_val_mAP
         if improved:
@@ -540,6 +558,9 @@ class ModelTrainer:
         opt = {k: (v.detach().to("cpu", copy=True) if torch.is_tensor(v) else v) for k, v in self.optimizer.state_dict().items()}
         state = {"epoch": epoch, "state_dict": snapshot(self.model), "optimizer": opt,
                  "scheduler": self.scheduler.state_dict(), "best_val_loss": self.best_val_loss, "best_val_mAP": self.best_val_mAP}
+        if getattr(self.optimizer, "ema", None) is not None:
+            with self.optimizer.ema_weights():
+                state["live_state_dict"], state["state_dict"] = state["state_dict"], snapshot(self.model)
         ckpt_dir = getattr(self.config, "checkpoint_dir", None)
         if self.rank == 0:
             if improved and ckpt_dir:
@@ -562,6 +583,8 @@ class ModelTrainer:
                 if self._loss_scaling:                   # one small read; the epoch's statistics have synchronised already
                     rec = self.optimizer.dev_ls.cpu()
                     line["loss_scale"], line["skipped_steps"] = float(rec.view(torch.float32)[0]), int(rec[7])
+                if getattr(self.optimizer, "ema", None) is not None:
+                    line["ema"] = True
                 print(json.dumps(line), flush=True)
         return self.best_val_mAP
 
@@ -693,6 +716,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
                     help="feature concatenation (concat_dim = -1): train on the fused chains, projection layer included")
     ap.add_argument("--loss-scale", default=None, metavar="{off,dynamic,<number>}",
                     help="loss scaling on the device for float16 gradients: dynamic, or a number for a static scale (training.loss_scale)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="validate and checkpoint an exponential moving average of the weights with decay D (training.ema_decay)")
     ap.add_argument("--device-metrics", action="store_true", help="log loss and metric inputs on the device inside the step, read once per epoch")
     args = ap.parse_args()
     rank, world, local = parallel.init_from_env()
@@ -709,6 +734,8 @@ def main(default_task="multilabel", default_motion_key="flow"):
         over["fused_feature_training"] = True
     if args.loss_scale is not None:
         over["loss_scale"] = args.loss_scale
+    if args.ema_decay is not None:
+        over["ema_decay"] = args.ema_decay
     if args.config:
         cfg = Config.from_yaml(args.config, **over)
     else:

@@ -134,6 +134,8 @@ SIGNATURES = {
     "vmc_grad_accumulate": (I, [P, P, P, Z, F, I, P]),
     "vmc_loss_scale_workspace_bytes": (Z, [Z]),
     "vmc_loss_scale_check": (I, [P, Z, P, P, P, P, P, Z, P]),
+    "vmc_ema_update": (I, [P, P, Z, F, I, ctypes.c_longlong, P, P, P]),
+    "vmc_ema_swap": (I, [P, P, Z, P]),
     "vmc_lora_down_concat": (I, [P, I, P, I, P, I, I, I, I, I, F, I, I, P]),
     "vmc_lora_wgrad_tn_workspace_bytes": (Z, [I, I, I]),
     "vmc_lora_wgrad_tn": (I, [P, I, P, I, P, I, I, I, I, P, Z, I, P]),

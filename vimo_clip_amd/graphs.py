@@ -193,6 +193,8 @@ class GraphedTrainStep:
         live = live if clip is None else live + (clip,)
         ls = getattr(o, "dev_ls", None)                # loss scaling on: a warm-up leaves S, the tracker and the counters as it found them
         live = live if ls is None else live + (ls,)
+        ema = getattr(o, "ema", None)                  # weight average on: a warm-up run's update is taken back with the parameters'
+        live = live if ema is None else live + (ema,)
         return live + self.extra_live
 
     def _capture(self, fn, inputs):

@@ -6,12 +6,14 @@ backward kernels write gradients in place (autograd_ops._grad_out), the optimise
 launch over the whole arena (28 B/parameter of HBM traffic), and data-parallel training all-reduces the
 flat gradient buffer in large buckets (parallel.py).  Every backward OVERWRITES its gradient slots;
 ``GradArena.accumulate`` is the opt-in way to sum the gradients of several micro-batches (vmc_grad_accumulate,
-DESIGN.md "Gradient accumulation").  Mirrors ``torch.optim.Adam(lr)`` (train.py:66) and
+DESIGN.md "Gradient accumulation"); ``FusedAdam.enable_ema`` the opt-in way to keep an exponential moving average of the masters beside
+them (vmc_ema_update behind every step, ``ema_weights()`` to compute with it).  Mirrors ``torch.optim.Adam(lr)`` (train.py:66) and
 ``torch.optim.AdamW(lr=1e-4, weight_decay=0.1)`` + ``CosineAnnealingLR(T_max=epochs, eta_min=1e-6)``
 (TFAM/train_and_eval.py:53-56) in arithmetic.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -155,6 +157,7 @@ class FusedAdam:
         self.v = torch.zeros_like(arena.flat_param)
         self.step_count = 0
         self.param_groups = [{"lr": lr}]          # what LR schedulers / loggers poke at
+        self.ema = None                            # fp32 average of flat_param (enable_ema); None = off: nothing allocated or launched
 
     def zero_grad(self, set_to_none: bool = False):
         """Does nothing, for loops that call it every step: each backward overwrites its arena slots, so there is nothing to clear
@@ -329,6 +332,73 @@ class FusedAdam:
             raise IndexError("more dropout call sites per step than FusedAdam.N_SEEDS")
         return (1 << 63) | (self.dev_state.data_ptr() + 8 * (2 + i))
 
+    # ---- exponential moving average of the weights -------------------------------------------------------------
+    def enable_ema(self, decay: float = 0.9999, warmup: bool = True):
+        """Keep ``self.ema``, an fp32 average of ``arena.flat_param`` (a copy of it at this moment): every ``step()`` then enqueues
+        one more streaming launch behind the update, ``ema = lerp(ema, p, w)`` over the whole arena (vmc_ema_update, 12 B per
+        parameter), with w = 1 - decay rounded once from float64, or with ``warmup`` max(1 - decay, 9 / (10 + t)) -- the usual
+        decay_t = min(decay, (1 + t) / (10 + t)).  t is ``step_count`` in host-state mode; in device-state mode the kernel reads the
+        step count and the loss scale's skip flag from device memory, so a captured step replays with the right weight and a skipped
+        step leaves the average's bytes (and, the tick having been taken back, its warm-up count) alone.  Nothing is exchanged under
+        data parallelism: the average is a function of parameters that are the same on every rank.  Allocates: raises inside a capture."""
+        decay = float(decay)
+        if not 0.0 < decay < 1.0:
+            raise ValueError(f"enable_ema: decay must lie strictly between 0 and 1, got {decay}")
+        p = self.arena.flat_param
+        if p.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("enable_ema while a graph is being captured: enable it before the first captured step")
+        self._ema_w = ctypes.c_float(1.0 - decay).value      # the one rounding of 1 - decay, from float64
+        self._ema_warmup = bool(warmup)
+        self._ema_active = False
+        self.ema = p.detach().clone()
+        return self
+
+    def disable_ema(self):
+        if self.ema is not None and self._ema_active:
+            raise RuntimeError("disable_ema inside ema_weights(): the average holds the live weights, leave the context first")
+        self.ema = None
+
+    def _ema_update(self):
+        a, state = self.arena, getattr(self, "dev_state", None)
+        check(lib.vmc_ema_update(ptr(self.ema), ptr(a.flat_param), a.numel, self._ema_w, int(self._ema_warmup),
+                                 0 if state is not None else self.step_count, ptr(state), None if state is None else self._skip_ptr(),
+                                 stream()), "ema_update")
+
+    def _ema_swap(self):
+        a = self.arena
+        check(lib.vmc_ema_swap(ptr(a.flat_param), ptr(self.ema), a.numel, stream()), "ema_swap")
+        invalidate_weight_copies(self)                 # the 16-bit copies follow the masters; a new weight epoch for every inference cache
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model computes with the AVERAGED weights: ``flat_param`` and ``ema`` trade places bit for bit
+        (vmc_ema_swap: no third arena-sized buffer), the 16-bit compute copies are refreshed and the weight epoch moves; the same
+        again on exit, after which the live weights are back as they were.  For evaluation and export only: ``step()`` raises
+        inside it.  Raises when the average is off, inside a capture, when nested, while a gradient accumulation is pending and
+        while an overlapped step is open."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights: the average is off, enable_ema() comes first")
+        if self.ema.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ema_weights while a graph is being captured: a capture must not freeze the averaged weights in")
+        if self._ema_active:
+            raise RuntimeError("ema_weights does not nest")
+        if self.arena.pending:
+            raise RuntimeError(f"ema_weights with {self.arena.pending} micro-step(s) of a gradient accumulation pending: finish the step first")
+        if getattr(self, "_step_open", False):
+            raise RuntimeError("ema_weights while an overlapped optimiser step is open: call step() first")
+        self._ema_swap()
+        self._ema_active = True
+        try:
+            yield self
+        finally:
+            self._ema_swap()
+            self._ema_active = False
+
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` with the averaged values (the reference's keys), cloned to the CPU; taken under the swap."""
+        with self.ema_weights():
+            return {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+
     # ---- optimiser step overlapped with the backward ----------------------------------------------------------------------
     def enable_backward_overlap(self, groups):
         """groups: lists of parameters, each a contiguous run of the arena, whose gradients become final TOGETHER during the
@@ -407,6 +477,8 @@ class FusedAdam:
         ov = getattr(self, "_ov", None)
         if ov is None or i >= len(ov["ranges"]) or ov["done"][i]:
             return
+        if self.ema is not None and self._ema_active:
+            raise RuntimeError("a training backward inside ema_weights(): the arena holds the averaged weights, leave the context first")
         lo, hi, ids = ov["ranges"][i]
         self._open_step()
         side = ov["stream"]
@@ -421,6 +493,8 @@ class FusedAdam:
         from . import autograd_ops
         autograd_ops.wgrad_queue.flush()               # normally empty: the backward pass flushes its grouped weight gradients itself
         a = self.arena
+        if self.ema is not None and self._ema_active:
+            raise RuntimeError("FusedAdam.step inside ema_weights(): the arena holds the averaged weights, leave the context first")
         if a.pending:
             raise RuntimeError(f"FusedAdam.step with {a.pending} micro-step(s) folded into the accumulator and not finalised: the arena "
                                "holds only the last micro-batch's gradient.  Call arena.accumulate(weight, final=True) after the last "
@@ -450,6 +524,8 @@ class FusedAdam:
             ov["done"] = [False] * len(ov["ranges"])
             ov["used"] = False
             self._step_open = False
+            if self.ema is not None:                   # on the main stream, behind the join: every range has its new values
+                self._ema_update()
             return
         if dev_mode and self.dev_ls is not None:    # found-inf check, unscaled norm, hyper[3] = base_scale / S * coefficient, scale update
             check(lib.vmc_loss_scale_check(ptr(a.flat_grad), a.numel, ptr(self.dev_ls), ptr(self.dev_hyper),
@@ -463,10 +539,14 @@ class FusedAdam:
         self._open_step()
         if dev_mode and self._fused_update():          # AdamW + refresh of the 16-bit copies in one pass over the masters
             self._step_open = False
+            if self.ema is not None:
+                self._ema_update()
             return
         self._update_range(0, a.numel, grad_scale)
         self._step_open = False
         invalidate_weight_copies(self)
+        if self.ema is not None:
+            self._ema_update()
 
     FUSED_CAST = os.environ.get("VMC_ADAM_FUSED_CAST", "1") != "0"      # builder A/B switch
 
@@ -515,6 +595,8 @@ class FusedAdam:
         if getattr(self, "dev_ls", None) is not None:
             sd["step"] = int(self.dev_state[0].item())
             sd["loss_scale"] = self.dev_ls.detach().cpu().clone()
+        if self.ema is not None:
+            sd["ema"], sd["ema_one_minus_decay"], sd["ema_warmup"] = self.ema, self._ema_w, self._ema_warmup
         return sd
 
     def load_state_dict(self, sd):
@@ -523,6 +605,11 @@ class FusedAdam:
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
         self.param_groups[0]["lr"] = sd["lr"]
+        if sd.get("ema") is not None:                         # the average and its weight; allocated here when it was not on yet
+            if self.ema is None:
+                self.ema, self._ema_active = torch.empty_like(self.arena.flat_param), False
+            self.ema.copy_(sd["ema"])
+            self._ema_w, self._ema_warmup = float(sd["ema_one_minus_decay"]), bool(sd["ema_warmup"])
         if getattr(self, "dev_state", None) is not None:      # device-state mode: the step count and lr the kernels read
             self.dev_state[0] = self.step_count
             if sd.get("loss_scale") is not None and self.dev_ls is not None:      # S, factors, interval, tracker, counters

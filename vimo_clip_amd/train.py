@@ -8,10 +8,13 @@ segments.  ``--single_label`` is the MammalNet variant (train_frame_diff_mn.py:8
 batch as up to N micro-batches whose gradients are summed in the arena (optim.GradArena.accumulate); 1 is the loop as it was.
 ``--compute_dtype f16`` trains in float16 and ``--loss_scale dynamic|<number>`` (neither in the reference) keeps its gradients in
 range: the optimiser moves to device-state mode and scales, checks and skips on the device (optim.FusedAdam.enable_loss_scaling).
+``--ema_decay D`` (not in the reference) keeps an exponential moving average of the trained weights on the device
+(optim.FusedAdam.enable_ema): validation and ``student_best.pth`` use the average, the per-epoch files the live weights.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import time
 
@@ -131,9 +134,33 @@ def patch_dropout_kwargs(args, rank: int = 0) -> dict:
     return {"patch_dropout": p, "patch_dropout_seed": PATCH_DROPOUT_SEED + int(rank)}
 
 
+def _ema_decay_arg(text):
+    """``--ema_decay`` values: a decay 0 < D < 1."""
+    try:
+        d = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--ema_decay needs a number, got {text!r}") from None
+    if not 0.0 < d < 1.0:
+        raise argparse.ArgumentTypeError(f"--ema_decay must satisfy 0 < D < 1, got {text!r}")
+    return d
+
+
+def ema_kwargs(args):
+    """``--ema_decay D [--ema_no_warmup]`` -> the keyword arguments of ``FusedAdam.enable_ema``; None (the default): the average is
+    off and the loop is the one it was."""
+    decay = getattr(args, "ema_decay", None)
+    if decay is None:
+        return None
+    if not 0.0 < float(decay) < 1.0:
+        raise ValueError(f"--ema_decay must satisfy 0 < D < 1, got {decay}")
+    return {"decay": float(decay), "warmup": not getattr(args, "ema_no_warmup", False)}
+
+
 def save_best(model, path: str) -> None:
     """The best-so-far checkpoint.  With live adapters it is written MERGED (lora.merged_state_dict: W + s B A, the reference's keys),
-    so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are."""
+    so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are.  With
+    ``--ema_decay`` the trainer calls it inside ``FusedAdam.ema_weights()``: the file then holds the averaged weights that were just
+    evaluated (merged from the averaged adapters)."""
     from .checkpoint import add_prefix, save_state_dict
     if getattr(model.visual_encoder, "lora", None) is None:
         return save_state_dict(model, path)
@@ -172,6 +199,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     accum = int(getattr(args, "accum_steps", 1))
     if accum < 1:                                           # before anything touches the device
         raise ValueError(f"--accum_steps must be at least 1, got {accum}")
+    ema = ema_kwargs(args)
     rank, world, local = parallel.init_from_env()
     device = f"cuda:{local}"
     E = embed_dim(args.clip_model_name)
@@ -204,6 +232,9 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     scaling = parse_loss_scale(getattr(args, "loss_scale", "off"))
     if scaling is not None:                                # the scaler lives in device memory: device-state mode, tick() per step
         optimizer.enable_device_state().enable_loss_scaling(**scaling)
+    if ema is not None:                                    # an fp32 average of the arena, updated behind every step on the device
+        optimizer.enable_ema(**ema)
+    averaged = optimizer.ema_weights if ema is not None else contextlib.nullcontext      # what is evaluated and written as the best
 
     def micro_loss(batch):
         emb, emb_d, logits = model(_frames(batch).to(device), **forward_kwargs)
@@ -242,12 +273,13 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
             optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=None if single else args.grad_clip_norm)
             nframes += frames.shape[0] * frames.shape[1]
         torch.cuda.synchronize()
-        vd, vc, vt = evaluate(model, val_set, device, args.distillation_loss_mode, args.class_positive_weight, args.batch_size, rank, world, single,
-                              collate, forward_kwargs)
-        if rank == 0 and ckpt_dir:                          # train.py:164-172: every epoch + the best-so-far copy
+        if rank == 0 and ckpt_dir:                          # train.py:164-172: every epoch (the live weights) + the best-so-far copy
             from .checkpoint import save_state_dict
             save_state_dict(model, f"{ckpt_dir}/student_epoch_{epoch + 1}.pth")
-            if vt < best:
+        with averaged():
+            vd, vc, vt = evaluate(model, val_set, device, args.distillation_loss_mode, args.class_positive_weight, args.batch_size, rank, world,
+                                  single, collate, forward_kwargs)
+            if rank == 0 and ckpt_dir and vt < best:
                 save_best(model, f"{ckpt_dir} - best/student_best.pth")
         best = min(best, vt)
         if rank == 0:
@@ -258,6 +290,8 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
             if scaling is not None:                         # one small read where the loop has already synchronised
                 rec = optimizer.dev_ls.cpu()
                 line["loss_scale"], line["skipped_steps"] = float(rec.view(torch.float32)[0]), int(rec[7])
+            if ema is not None:                             # the validation figures are those of the averaged weights
+                line["ema"] = True
             print(json.dumps(line), flush=True)
     return best
 
@@ -295,6 +329,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--patch_dropout", type=_patch_dropout_arg, default=argparse.SUPPRESS, metavar="P",
                    help="training only: every frame keeps its class token and max(1, int(g^2 (1 - P))) randomly drawn patch tokens, the "
                         "tower runs on those rows; evaluation sees every token; default 0 = nothing is dropped")
+    p.add_argument("--ema_decay", type=_ema_decay_arg, default=argparse.SUPPRESS, metavar="D",
+                   help="keep an exponential moving average of the trained weights on the device (decay D, e.g. 0.9999); validation runs "
+                        "on it and student_best.pth holds it; the per-epoch files keep the live weights; default off")
+    p.add_argument("--ema_no_warmup", action="store_true", default=argparse.SUPPRESS,
+                   help="with --ema_decay: the constant decay from the first step on, instead of min(D, (1 + t) / (10 + t))")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

@@ -46,6 +46,9 @@ def build_parser() -> argparse.ArgumentParser:
     arg("patch_dropout", type=float, default=0.0, metavar="P",
         help="training only: keep the class token and max(1, int(g^2 (1 - P))) random patch tokens per frame (train.patch_dropout_kwargs); "
              "0 = off")
+    arg("ema_decay", type=float, default=None, metavar="D",
+        help="evaluate and write the best checkpoint with an exponential moving average of the weights (train.ema_kwargs); default off")
+    arg("ema_no_warmup", action="store_true", help="with --ema_decay: the constant decay from the first step on")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
@@ -55,6 +58,7 @@ def train(args):
     student_train.parse_loss_scale(args.loss_scale)         # a malformed value fails before any file is opened
     if not 0.0 <= args.patch_dropout < 1.0:
         raise ValueError(f"--patch_dropout must satisfy 0 <= p < 1, got {args.patch_dropout}")
+    student_train.ema_kwargs(args)                           # --ema_decay outside (0, 1) fails here too
     size = tuple(args.spatial_size)
     sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
                                   raw_u8=args.device_resize) for path in (args.train_hdf5_path, args.val_hdf5_path))
