@@ -701,7 +701,7 @@ int vmc_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
  *          (with gradient clipping vmc_grad_clip_dev writes [3], with loss scaling vmc_loss_scale_check does: both below)
  * vmc_train_tick: t += 1, recomputes hyper[1..2] and the n_seeds seeds (splitmix of base seed, t and the index); enqueue it once
  * per step before the forward.  vmc_adam_step_dev = vmc_adam_step reading its four scalars from `hyper`.
- * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd, vmc_patch_keep_sample): a value < 2^63 is the
+ * SEED ARGUMENTS (vmc_dropout, vmc_postnorm_dropout_fwd, vmc_attention_fwd / _bwd, vmc_patch_keep_sample, vmc_drop_path_sample): a value < 2^63 is the
  * seed itself; with bit 63 set the low 63 bits are the ADDRESS of a u64 in device memory holding it (e.g. &state[2 + i]), read at
  * kernel start.
  * POOL LENGTH (the `_len` entries: vmc_mean_pool_len / _bwd_len, vmc_tfam_head_fwd_len, vmc_tfam_forward_len,
@@ -991,6 +991,42 @@ int vmc_assemble_tokens_keep(const void* xp, const float* cls, const float* pos,
 size_t vmc_assemble_tokens_keep_bwd_workspace_bytes(int F, int G, int D);
 int vmc_assemble_tokens_keep_bwd(const void* dx, const int* keep, void* dxp16, float* dcls, float* dpos, int F, int G, int Kp, int D,
                                  int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Stochastic depth that skips dropped frames, in the student's training tower (autograd_vit.py) -----------------
+ * Block l keeps K of the F frames of a forward; the block (its GEMMs, attention, backward, saved activations) runs on the K kept frames
+ * and the stream of the others passes by:  out[f] = x[f] (f dropped),  out[f] = c x[f] + s Block(x)[f] (f kept),  s = F / K, c = 1 - s.
+ * A frame is `row` consecutive elements (N D of the token stream, D of the class rows); all tensors of a call share `dtype` (VMC_F32,
+ * VMC_BF16 or VMC_F16).  Five memory-bound launches: 16-byte accesses where row % (16 / element size) == 0 and the pointers are
+ * 16-byte aligned, element by element otherwise; fp32 arithmetic and one rounding at the store; no floating-point atomics: the same
+ * bits every call.  Frame ids and slots are read from device memory, which the host cannot validate: ids are clamped into 0..F-1.
+ * Common to the four data entries, before any launch: a NULL pointer or row == 0 -> VMC_E_ARG; a dtype outside the three ->
+ * VMC_E_DTYPE; a pointer that is not a multiple of its element size -> VMC_E_ALIGN.
+ *
+ * vmc_drop_path_sample: keep[0:K] = the K frames with the smallest (key, f), key = hash32(seed, block F + f) (the counter hash of
+ * vmc_dropout and vmc_patch_keep_sample), written in ascending f; slot[f] = the position of f in keep, -1 where f is dropped.  seed:
+ * see "SEED ARGUMENTS".  keep int32 [K], slot int32 [F].  One launch of one workgroup (keys in LDS, rank by counting).
+ * VMC_E_ARG: keep or slot NULL, block < 0.  VMC_E_SHAPE: not 1 <= K <= F <= 8192. */
+int vmc_drop_path_sample(uint64_t seed, int block, int F, int K, int* keep, int* slot, void* stream);
+
+/* vmc_frame_gather: dst[j, :] = src[keep[j], :], bit copies.  src [F, row], dst [K, row].  HBM: K row read and written.
+ * VMC_E_SHAPE: not 1 <= K <= F. */
+int vmc_frame_gather(const void* src, const int* keep, void* dst, int F, int K, size_t row, int dtype, void* stream);
+
+/* vmc_frame_scatter_add: dx[f, :] = dpass[f, :] + (slot[f] >= 0 ? dsub[slot[f], :] : 0): the backward of a gather that also passes
+ * its input on; one fp32 add, rows with slot < 0 are bit copies of dpass.  dpass, dx [F, row]; dsub [K, row] with every slot below K.
+ * HBM: (F + K) row read, F row written.  VMC_E_SHAPE: F < 1. */
+int vmc_frame_scatter_add(const void* dpass, const void* dsub, const int* slot, void* dx, int F, size_t row, int dtype, void* stream);
+
+/* vmc_drop_path_merge: out[f, :] = slot[f] >= 0 ? c x[f, :] + s y[slot[f], :] : x[f, :] (a bit copy).  Two fp32 products and their
+ * sum, each rounded (no contraction), then the store.  x, out [F, row]; y [K, row].  HBM: (F + K) row read, F row written.
+ * VMC_E_SHAPE: F < 1. */
+int vmc_drop_path_merge(const void* x, const void* y, const int* slot, void* out, int F, size_t row, float c, float s, int dtype,
+                        void* stream);
+
+/* vmc_drop_path_merge_bwd: dx[f, :] = slot[f] >= 0 ? c dout[f, :] : dout[f, :] (a bit copy);  dy[j, :] = s dout[keep[j], :]; one launch
+ * writes both.  dout, dx [F, row]; dy [K, row].  HBM: (F + K) row read and written.  VMC_E_SHAPE: not 1 <= K <= F. */
+int vmc_drop_path_merge_bwd(const void* dout, const int* keep, const int* slot, void* dx, void* dy, int F, int K, size_t row, float c,
+                            float s, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,11 @@ SIGNATURES = {
     "vmc_assemble_tokens_keep": (I, [P, P, P, P, P, I, I, I, I, I, I, P]),
     "vmc_assemble_tokens_keep_bwd_workspace_bytes": (Z, [I, I, I]),
     "vmc_assemble_tokens_keep_bwd": (I, [P, P, P, P, P, I, I, I, I, I, I, P, Z, P]),
+    "vmc_drop_path_sample": (I, [ctypes.c_uint64, I, I, I, P, P, P]),
+    "vmc_frame_gather": (I, [P, P, P, I, I, Z, I, P]),
+    "vmc_frame_scatter_add": (I, [P, P, P, P, I, Z, I, P]),
+    "vmc_drop_path_merge": (I, [P, P, P, P, I, Z, F, F, I, P]),
+    "vmc_drop_path_merge_bwd": (I, [P, P, P, P, P, I, I, Z, F, F, I, P]),
 }
 
 

@@ -705,6 +705,45 @@ class AssembleTokensKeepFn(torch.autograd.Function):
         return dxp, _deliver(cls, dcls), _deliver(pos, dpos), None, None
 
 
+class FrameGatherFn(torch.autograd.Function):
+    """Drop path, in front of a block: xs [F*N, D] -> (x_sub [K*N, D], the rows of the frames ``keep`` names, and x_pass, xs itself).
+    Linear, so nothing but keep / slot is kept.  The backward adds the two gradients in its own launch (vmc_frame_scatter_add), the
+    pattern of ``layernorm(..., passthrough=True)``."""
+
+    @staticmethod
+    def forward(ctx, xs, keep, slot):
+        F, K = slot.numel(), keep.numel()
+        ctx.slot, ctx.meta = slot, (F, K)
+        return ops.frame_gather(xs.view(F, -1), keep).view(K * (xs.shape[0] // F), xs.shape[1]), xs.view(xs.shape)
+
+    @staticmethod
+    def backward(ctx, dsub, dpass):
+        F, K = ctx.meta
+        if dpass is None:
+            dpass = torch.zeros((F * (dsub.shape[0] // K), dsub.shape[1]), dtype=dsub.dtype, device=dsub.device)
+        if dsub is None:
+            return dpass, None, None
+        dx = ops.frame_scatter_add(dpass.contiguous().view(F, -1), dsub.contiguous().view(K, -1), ctx.slot)
+        return dx.view(dpass.shape), None, None
+
+
+class DropPathMergeFn(torch.autograd.Function):
+    """Drop path, behind a block: out[f] = (1 - s) x_pass[f] + s y_sub[slot[f]] for a kept frame, x_pass[f] (the same bits) for a
+    dropped one; x_pass [F*n, D], y_sub [K*n, D] (n = N token rows per frame, or 1 for the class rows of a cls_only last block)."""
+
+    @staticmethod
+    def forward(ctx, x_pass, y_sub, keep, slot, s):
+        F = slot.numel()
+        ctx.keep, ctx.slot, ctx.s = keep, slot, s
+        return ops.drop_path_merge(x_pass.contiguous().view(F, -1), y_sub.contiguous().view(keep.numel(), -1), slot, s).view(x_pass.shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        F, K = ctx.slot.numel(), ctx.keep.numel()
+        dx, dy = ops.drop_path_merge_bwd(dout.contiguous().view(F, -1), ctx.keep, ctx.slot, ctx.s)
+        return dx.view(dout.shape), dy.view(K * (dout.shape[0] // F), dout.shape[1]), None, None, None
+
+
 class DropoutFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p, seed):

@@ -9,6 +9,10 @@ there (_BlockFn); ``saved_activation_bytes`` counts what either mode keeps.
 
 ``model.patch_dropout = p > 0`` (training with gradients only) keeps the class token and Kp = max(1, int(g^2 (1 - p))) randomly drawn
 patch tokens of every frame: the patch GEMM, the tower and their backward run on Kp + 1 rows per frame (``patch_keep_for``).
+
+``model.drop_path = p > 0`` (training with gradients only) is stochastic depth per frame: block l keeps K_l = max(1, int(F (1 - p_l)))
+of the F frames, p_l = p l / max(1, L - 1); the block runs on the kept frames alone and its output is merged back into the stream
+with the scale F / K_l (``drop_keep_for``).
 """
 from __future__ import annotations
 
@@ -43,8 +47,61 @@ def patch_keep_for(model, F: int, device):
     return ops.patch_keep_sample(seed, F, g * g, ops.patch_keep_count(g * g, p), device)
 
 
-def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only: bool = True, keep: torch.Tensor = None):
+DROP_PATH_SALT = 0xD509A7B1C0FFEE11      # keeps the drop-path stream apart from the patch-dropout stream of the same base seed
+
+
+def drop_keep_for(model, F: int, device):
+    """Per residual block None (the block runs on every frame, as it always did) or (keep int32 [K_l] ascending, slot int32 [F], s_l =
+    F / K_l): the frames block l keeps in this training forward.  All None -- and nothing drawn -- when ``model.drop_path`` is 0, the
+    model is in eval mode, or no gradient is being recorded; a block whose K_l equals F is None as well (block 0 always).  The seed
+    is ``model.drop_path_seed_address`` verbatim when set (a device address with bit 63: a captured step draws anew on every replay);
+    otherwise the splitmix finaliser of ``model.drop_path_seed`` and the number of forwards this model has drawn for so far.  The block
+    index goes into the counter of the hash, so one seed serves every block of a forward."""
+    L = len(model.transformer.resblocks)
+    p = float(getattr(model, "drop_path", 0.0) or 0.0)
+    if p <= 0.0 or not model.training or not torch.is_grad_enabled():
+        return [None] * L
+    if not p < 1.0:
+        raise ValueError(f"VisionTransformer.drop_path must be in [0, 1), got {p}")
+    counts = [ops.drop_path_keep_count(F, ops.drop_path_rate(p, l, L)) for l in range(L)]
+    if all(K == F for K in counts):
+        return [None] * L
+    if F > ops.DROP_PATH_MAX_F:
+        raise ValueError(f"drop path draws among at most {ops.DROP_PATH_MAX_F} frames per forward, got {F}: split the batch")
+    seed = getattr(model, "drop_path_seed_address", None)
+    if seed is None:
+        calls = getattr(model, "_drop_path_calls", 0)
+        model._drop_path_calls = calls + 1
+        seed = _mix64(_mix64(int(getattr(model, "drop_path_seed", 0)) ^ DROP_PATH_SALT) + calls) >> 1          # a value below 2^63
+    return [None if K == F else (*ops.drop_path_sample(seed, l, F, K, device), F / K) for l, K in enumerate(counts)]
+
+
+def _given_drop_keep(model, drop_keep, F: int):
+    """``drop_keep=``: a list of length L of None or an int32 device tensor [K_l] of ascending frame ids -> the triples of
+    ``drop_keep_for`` (the inverse of every keep set is plain index plumbing, once per forward)."""
+    L = len(model.transformer.resblocks)
+    if not torch.is_grad_enabled() or not model.training:
+        raise ValueError("drop_keep needs the training forward (train() mode with gradients enabled)")
+    if not isinstance(drop_keep, (list, tuple)) or len(drop_keep) != L:
+        raise ValueError(f"drop_keep must be a list of {L} entries (one per residual block), each None or an int32 tensor of frame ids")
+    out = []
+    for k in drop_keep:
+        if k is None:
+            out.append(None)
+            continue
+        if k.dtype != torch.int32 or k.dim() != 1 or not 1 <= k.numel() <= F or not k.is_contiguous():
+            raise ValueError(f"a drop_keep entry must be a contiguous int32 vector of 1..{F} frame ids, got {k.dtype} {tuple(k.shape)}")
+        slot = torch.full((F,), -1, dtype=torch.int32, device=k.device)
+        slot[k.long().clamp(0, F - 1)] = torch.arange(k.numel(), dtype=torch.int32, device=k.device)
+        out.append((k, slot, F / k.numel()))
+    return out
+
+
+def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only: bool = True, keep: torch.Tensor = None,
+                     drop_keep=None):
     """x: u8 [F,3,R,R] frames or float pixel values.  Returns (the final residual stream, F, N, rows_are_cls).
+    drop_keep: per block None or the frames it keeps (``_given_drop_keep``); None: ``drop_keep_for(model)`` decides (every block runs
+    on every frame unless ``model.drop_path`` asks otherwise).
     keep: int32 [F, Kp] device tensor of ascending patch ids per frame: only those patches (and the class token) enter the tower and
     the N returned is Kp + 1; None: ``patch_keep_for(model)`` decides (nothing is dropped unless ``model.patch_dropout`` asks for it).
     cls_only: only x[:, 0] of the last block reaches ln_post, so its out_proj / ln_2 / MLP run on the F class rows (forward and,
@@ -64,6 +121,7 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
     N = g * g + 1
     if keep is None:
         keep = patch_keep_for(model, F, model.class_embedding.device)
+    drop = drop_keep_for(model, F, model.class_embedding.device) if drop_keep is None else _given_drop_keep(model, drop_keep, F)
     with torch.no_grad():   # the input frames carry no gradient
         if x.dtype == torch.uint8:
             x, wrap_quirk = model.fit_frames_u8(x, wrap_quirk)
@@ -83,23 +141,38 @@ def vit_tokens_train(model, x: torch.Tensor, wrap_quirk: bool = False, cls_only:
         xs = ag.cast(xs, model.residual_dtype)
     blocks = list(model.transformer.resblocks)
     for i, blk in enumerate(blocks):
-        if recompute == "block":
-            xs = _BlockFn.apply(xs, (F, N, H, dt16, model.residual_dtype == torch.float32, cls_only and i + 1 == len(blocks)),
-                                *(blk.get_parameter(name) for name in _BLOCK_PARAMS))
-            continue
+        cls = cls_only and i + 1 == len(blocks)
         sites = lora.blocks[i] if lora is not None else {}
-        h, xs = ag.layernorm(xs, blk.ln_1.weight, blk.ln_1.bias, dt16, passthrough=True)
-        qkv = _linear(sites.get("attn.in_proj"), h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
-        o = ag.SelfAttnPackedFn.apply(qkv, None, F, N, H)
-        if cls_only and i + 1 == len(blocks):
-            o, xs = _ClsRowsFn.apply(o, F, N), _ClsRowsFn.apply(xs, F, N)
-        xs = _linear(sites.get("attn.out_proj"), o, blk.attn.out_proj.weight, blk.attn.out_proj.bias, res=xs,
-                     out_f32=(model.residual_dtype == torch.float32))
-        h, xs = ag.layernorm(xs, blk.ln_2.weight, blk.ln_2.bias, dt16, passthrough=True)
-        u = _linear(sites.get("mlp.c_fc"), h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=ops.ACT_QUICKGELU)
-        xs = _linear(sites.get("mlp.c_proj"), u, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, res=xs,
-                     out_f32=(model.residual_dtype == torch.float32))
+        if drop[i] is None:
+            xs = _block(model, blk, sites, xs, F, N, cls, recompute)
+            continue
+        # drop path: the block sees the K kept frames only; the stream of the others passes by, bit for bit
+        keep_l, slot_l, s_l = drop[i]
+        x_sub, xs = ag.FrameGatherFn.apply(xs, keep_l, slot_l)
+        y_sub = _block(model, blk, sites, x_sub, keep_l.numel(), N, cls, recompute)
+        if cls:
+            xs = _ClsRowsFn.apply(xs, F, N)
+        xs = ag.DropPathMergeFn.apply(xs, y_sub, keep_l, slot_l, s_l)
     return xs, F, N, cls_only
+
+
+def _block(model, blk, sites, xs, F, N, cls, recompute):
+    """One residual block on the F frames of xs [F*N, D]; cls: the last block under cls_only, which returns the F class rows."""
+    dt16, H = model.compute_dtype, model.heads
+    if recompute == "block":
+        return _BlockFn.apply(xs, (F, N, H, dt16, model.residual_dtype == torch.float32, cls),
+                              *(blk.get_parameter(name) for name in _BLOCK_PARAMS))
+    h, xs = ag.layernorm(xs, blk.ln_1.weight, blk.ln_1.bias, dt16, passthrough=True)
+    qkv = _linear(sites.get("attn.in_proj"), h, blk.attn.in_proj_weight, blk.attn.in_proj_bias)
+    o = ag.SelfAttnPackedFn.apply(qkv, None, F, N, H)
+    if cls:
+        o, xs = _ClsRowsFn.apply(o, F, N), _ClsRowsFn.apply(xs, F, N)
+    xs = _linear(sites.get("attn.out_proj"), o, blk.attn.out_proj.weight, blk.attn.out_proj.bias, res=xs,
+                 out_f32=(model.residual_dtype == torch.float32))
+    h, xs = ag.layernorm(xs, blk.ln_2.weight, blk.ln_2.bias, dt16, passthrough=True)
+    u = _linear(sites.get("mlp.c_fc"), h, blk.mlp.c_fc.weight, blk.mlp.c_fc.bias, act=ops.ACT_QUICKGELU)
+    return _linear(sites.get("mlp.c_proj"), u, blk.mlp.c_proj.weight, blk.mlp.c_proj.bias, res=xs,
+                   out_f32=(model.residual_dtype == torch.float32))
 
 
 def _linear(site, x, weight, bias, **kw):
@@ -185,7 +258,7 @@ class _BlockFn(torch.autograd.Function):
 
 
 def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes16: int = 2, residual_bytes: int = 4,
-                           cls_only: bool = True, tokens: int = None) -> int:
+                           cls_only: bool = True, tokens: int = None, drop_path: float = 0.0) -> int:
     """Bytes the residual blocks of the training forward keep for the backward pass (what the per-op Functions of autograd_ops
     hand to ``save_for_backward``; the patch GEMM, ln_pre, ln_post and the projection are not counted).
     geometry: a model name or (resolution, patch, width, layers, heads, output_dim).
@@ -194,7 +267,9 @@ def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes
     (mean, rstd) pairs (16).  With cls_only the last block keeps everything after its attention for the F class rows only.
     "block": one input stream per block, r D bytes per row.  During the backward one recomputed block ("none" with one layer, the
     last block's class-row shortcut aside) is alive on top of that.
-    tokens: token rows per frame instead of the geometry's g^2 + 1 (patch dropout: Kp + 1)."""
+    tokens: token rows per frame instead of the geometry's g^2 + 1 (patch dropout: Kp + 1).
+    drop_path: block l keeps what it keeps today for K_l = max(1, int(F (1 - p_l))) of the F frames, p_l = drop_path l / max(1, L - 1)
+    (the gather and the merge around it keep two int32 vectors, not counted)."""
     if recompute not in RECOMPUTE_MODES:
         raise ValueError(f"recompute must be one of {RECOMPUTE_MODES}, got {recompute!r}")
     if isinstance(geometry, str):
@@ -206,16 +281,19 @@ def saved_activation_bytes(geometry, frames: int, recompute: str = "none", bytes
         if not 2 <= tokens <= N:
             raise ValueError(f"tokens must be in 2..{N} for this geometry, got {tokens}")
         N = tokens
-    rows, r, b = frames * N, residual_bytes, bytes16
+    if not 0.0 <= float(drop_path) < 1.0:
+        raise ValueError(f"drop_path must satisfy 0 <= p < 1, got {drop_path}")
+    r, b = residual_bytes, bytes16
+    kept = [ops.drop_path_keep_count(frames, ops.drop_path_rate(drop_path, l, L)) for l in range(L)]      # all `frames` at 0
     if recompute == "block":
-        return L * rows * r * D
+        return sum(K * N * r * D for K in kept)
     attn_half = (r + 5 * b) * D + 4 * H + 8          # stream at ln_1, ln_1 output, qkv, attention output; lse; (mean, rstd)
     mlp_half = (r + 9 * b) * D + 8                   # stream at ln_2, ln_2 output, z, u; (mean, rstd)
-    full = rows * (attn_half + mlp_half)
+    full = N * (attn_half + mlp_half)                # per frame
     if not cls_only:
-        return L * full
+        return sum(K * full for K in kept)
     # the last block: out_proj reads a gathered copy of the class rows of the attention output (one more 16-bit row), then F rows
-    return (L - 1) * full + rows * attn_half + frames * (b * D + mlp_half)
+    return sum(K * full for K in kept[:-1]) + kept[-1] * (N * attn_half + b * D + mlp_half)
 
 
 class _ClsRowsFn(torch.autograd.Function):
@@ -273,9 +351,10 @@ class _ProjFn(torch.autograd.Function):
         return dx, ag._deliver(proj, out)
 
 
-def vit_forward_train(model, x: torch.Tensor, wrap_quirk: bool = False, keep: torch.Tensor = None) -> torch.Tensor:
-    """[F,3,R,R] -> [F,E] f32 embeddings, differentiable w.r.t. every ViT parameter.  keep: see vit_tokens_train."""
-    xs, F, N, rows_are_cls = vit_tokens_train(model, x, wrap_quirk, cls_only=getattr(model, "cls_only_last_block", True), keep=keep)
+def vit_forward_train(model, x: torch.Tensor, wrap_quirk: bool = False, keep: torch.Tensor = None, drop_keep=None) -> torch.Tensor:
+    """[F,3,R,R] -> [F,E] f32 embeddings, differentiable w.r.t. every ViT parameter.  keep, drop_keep: see vit_tokens_train."""
+    xs, F, N, rows_are_cls = vit_tokens_train(model, x, wrap_quirk, cls_only=getattr(model, "cls_only_last_block", True), keep=keep,
+                                              drop_keep=drop_keep)
     cls = xs if rows_are_cls else _ClsRowsFn.apply(xs, F, N)
     h = ag.layernorm(cls, model.ln_post.weight, model.ln_post.bias, model.compute_dtype)
     return _ProjFn.apply(h, model.proj)

@@ -108,6 +108,12 @@ class VisionTransformer(nn.Module):
         self.patch_dropout = 0.0
         self.patch_dropout_seed = 0              # base of the keep-set stream (mixed with a per-model call counter) ...
         self.patch_dropout_seed_address = None   # ... or a seed argument in device-address form, used as it is
+        # training forward with gradients, train() mode: stochastic depth per frame.  Block l keeps max(1, int(F (1 - p l / (L - 1)))) of
+        # the F frames and runs on those alone (autograd_vit.drop_keep_for; DINOv2's subset form).  0: every block sees every frame, and
+        # none of the drop-path launches
+        self.drop_path = 0.0
+        self.drop_path_seed = 0                  # base of the draw stream (mixed with a per-model call counter) ...
+        self.drop_path_seed_address = None       # ... or a seed argument in device-address form, used as it is
         self.frame_chunk = 256  # frames per pass (bounds activation memory; F*N*4D*2 B for the MLP buffer)
         self._init_weights()
 

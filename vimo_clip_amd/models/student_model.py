@@ -73,16 +73,21 @@ class FlowStudentModel(nn.Module):
     def __init__(self, clip_model_name="ViT-B/32", device="cuda", num_classes=140, alpha=0.1,
                  compute_dtype=torch.bfloat16, residual_dtype=torch.float32,
                  lora_rank=0, lora_alpha=None, lora_targets=("attn",), patch_dropout=0.0, patch_dropout_seed=0,
-                 recompute="none"):
+                 drop_path=0.0, drop_path_seed=0, recompute="none"):
         """recompute: "none" or "block" (VisionTransformer.recompute: the training forward keeps one stream per block and
         recomputes the block in the backward pass; same results, a fraction of the activation memory).
         lora_rank > 0: the tower is frozen and rank-r adapters on the `lora_targets` linears of every block are trained with the two
         heads (lora.add_lora; alpha defaults to 2 rank).  0: no adapters, the model and its ``state_dict`` are what they always were.
         patch_dropout: 0 <= p < 1; in train() mode with gradients every frame keeps its class token and max(1, int(g^2 (1 - p)))
-        randomly drawn patch tokens (VisionTransformer.patch_dropout), evaluation sees every token.  0: nothing is dropped."""
+        randomly drawn patch tokens (VisionTransformer.patch_dropout), evaluation sees every token.  0: nothing is dropped.
+        drop_path: 0 <= p < 1; stochastic depth per frame in train() mode with gradients: block l of L runs on max(1, int(F (1 - p l /
+        (L - 1)))) randomly drawn frames of the forward (VisionTransformer.drop_path), evaluation runs every block on every frame.
+        0: nothing is dropped."""
         super().__init__()
         if not 0.0 <= float(patch_dropout) < 1.0:
             raise ValueError(f"patch_dropout must satisfy 0 <= p < 1, got {patch_dropout}")
+        if not 0.0 <= float(drop_path) < 1.0:
+            raise ValueError(f"drop_path must satisfy 0 <= p < 1, got {drop_path}")
         if lora_rank and recompute != "none":
             raise ValueError("LoRA adapters are not supported together with recompute='block'")
         self.device = device
@@ -92,6 +97,8 @@ class FlowStudentModel(nn.Module):
         self.visual_encoder.recompute = recompute
         self.visual_encoder.patch_dropout = float(patch_dropout)
         self.visual_encoder.patch_dropout_seed = int(patch_dropout_seed)
+        self.visual_encoder.drop_path = float(drop_path)
+        self.visual_encoder.drop_path_seed = int(drop_path_seed)
         self.preprocess = _Preprocess(self.visual_encoder.input_resolution)
         embed_dim = self.visual_encoder.output_dim
         self.residual_mlp = ResidualMLP(embed_dim, alpha=alpha, compute_dtype=compute_dtype)
@@ -119,11 +126,13 @@ class FlowStudentModel(nn.Module):
             return ops.unit_f32_to_u8(fr.to(self.device).float()), False
         return fr.to(torch.uint8).to(self.device), True
 
-    def forward(self, flow_videos, *, unit_u8=False, patch_keep=None):
+    def forward(self, flow_videos, *, unit_u8=False, patch_keep=None, drop_path_keep=None):
         """flow_videos [B,T,3,H,W] -> (embeddings [B,T,E], embeddings_for_distillation [B,T,E], logits [B,C]).
         unit_u8: u8 input is taken as pixels already quantised the way to_pil_image quantises [0,1] floats (no wrap).
         patch_keep: int32 [B*T, Kp] device tensor of ascending patch ids, the tokens each frame keeps (training forward only;
-        None: drawn when ``patch_dropout`` > 0, in train() mode with gradients)."""
+        None: drawn when ``patch_dropout`` > 0, in train() mode with gradients).
+        drop_path_keep: one entry per residual block, None or an int32 device tensor [K_l] of ascending frame ids, the frames the block
+        runs on (training forward only; None: drawn when ``drop_path`` > 0, in train() mode with gradients)."""
         B, T = flow_videos.shape[:2]
         frames, wrap = self._frames_u8(flow_videos, unit_u8)
         train = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
@@ -131,8 +140,10 @@ class FlowStudentModel(nn.Module):
         # during training sees them; lora.merge_lora puts the model back on encode_frames_u8
         if patch_keep is not None and not train:
             raise ValueError("patch_keep needs the training forward (gradients enabled and trainable parameters)")
+        if drop_path_keep is not None and not train:
+            raise ValueError("drop_path_keep needs the training forward (gradients enabled and trainable parameters)")
         if train or getattr(self.visual_encoder, "lora", None) is not None:
-            emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=wrap, keep=patch_keep)          # [B*T, E] f32
+            emb = vit_forward_train(self.visual_encoder, frames, wrap_quirk=wrap, keep=patch_keep, drop_keep=drop_path_keep)   # [B*T, E] f32
         else:
             emb = self.visual_encoder.encode_frames_u8(frames, wrap_quirk=wrap)
         return self._heads(emb, train, B, T)

@@ -581,3 +581,83 @@ def assemble_tokens_keep_bwd(dx: torch.Tensor, keep: torch.Tensor, G: int, dtype
     check(lib.vmc_assemble_tokens_keep_bwd(ptr(dx), ptr(keep), ptr(dxp), ptr(dcls), ptr(dpos), F, G, Kp, D, dt(dx), dt(dtype16), ptr(ws),
                                            nbytes, stream()), "assemble_tokens_keep_bwd")
     return dxp, dcls, dpos
+
+
+# ---- stochastic depth that skips dropped frames (include/vmc.h) -----------------------------------------------------
+DROP_PATH_MAX_F = 8192
+
+
+def drop_path_rate(p: float, block: int, layers: int) -> float:
+    """p_l = p l / max(1, L - 1): the linear rule, block 0 never drops."""
+    return float(p) * block / max(1, layers - 1)
+
+
+def drop_path_keep_count(frames: int, p_l: float) -> int:
+    """K_l = max(1, int(F (1 - p_l))): the rounding of ``patch_keep_count``."""
+    return patch_keep_count(frames, p_l)
+
+
+def _check_frames(name: str, x: torch.Tensor, rows: int = None) -> int:
+    """x is a contiguous [rows, row] matrix of frames; returns row."""
+    if x.dim() != 2 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16, torch.float16) or x.shape[1] < 1 \
+            or (rows is not None and x.shape[0] != rows):
+        raise ValueError(f"{name}: expected a contiguous f32 / bf16 / f16 matrix"
+                         f"{'' if rows is None else f' of {rows} frames'}, got {x.dtype} {tuple(x.shape)}")
+    return x.shape[1]
+
+
+def _check_index(name: str, t: torch.Tensor, n: int = None) -> int:
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.numel() < 1 or (n is not None and t.numel() != n):
+        raise ValueError(f"{name} must be a contiguous int32 vector{'' if n is None else f' of {n}'}, got {t.dtype} {tuple(t.shape)}")
+    return t.numel()
+
+
+def drop_path_sample(seed: int, block: int, F: int, K: int, device):
+    """(keep int32 [K], slot int32 [F]): the K of F frames with the smallest (hash32(seed, block F + f), f), ascending, and the
+    position of every frame in keep (-1: dropped) (vmc_drop_path_sample).  seed: a value below 2^63 or a device address with bit 63."""
+    if F > DROP_PATH_MAX_F:
+        raise ValueError(f"drop path draws among at most {DROP_PATH_MAX_F} frames per forward, got {F}: split the batch")
+    keep = torch.empty(K, dtype=torch.int32, device=device)
+    slot = torch.empty(F, dtype=torch.int32, device=device)
+    check(lib.vmc_drop_path_sample(int(seed), int(block), F, K, ptr(keep), ptr(slot), stream()), "drop_path_sample")
+    return keep, slot
+
+
+def frame_gather(src: torch.Tensor, keep: torch.Tensor) -> torch.Tensor:
+    """src [F, row] -> [K, row], row j = src row keep[j], bit copies (vmc_frame_gather)."""
+    row, K = _check_frames("frame_gather: src", src), _check_index("keep", keep)
+    dst = torch.empty((K, row), dtype=src.dtype, device=src.device)
+    check(lib.vmc_frame_gather(ptr(src), ptr(keep), ptr(dst), src.shape[0], K, row, dt(src), stream()), "frame_gather")
+    return dst
+
+
+def frame_scatter_add(dpass: torch.Tensor, dsub: torch.Tensor, slot: torch.Tensor) -> torch.Tensor:
+    """dx[f] = dpass[f] + dsub[slot[f]] where slot[f] >= 0, dpass[f] elsewhere (vmc_frame_scatter_add)."""
+    row, F = _check_frames("frame_scatter_add: dpass", dpass), _check_index("slot", slot, dpass.shape[0])
+    if _check_frames("frame_scatter_add: dsub", dsub) != row or dsub.dtype != dpass.dtype or dsub.shape[0] > F:
+        raise ValueError("frame_scatter_add: dsub must hold at most F frames of dpass's row length and dtype")
+    dx = torch.empty_like(dpass)
+    check(lib.vmc_frame_scatter_add(ptr(dpass), ptr(dsub), ptr(slot), ptr(dx), F, row, dt(dpass), stream()), "frame_scatter_add")
+    return dx
+
+
+def drop_path_merge(x: torch.Tensor, y: torch.Tensor, slot: torch.Tensor, s: float) -> torch.Tensor:
+    """out[f] = (1 - s) x[f] + s y[slot[f]] where slot[f] >= 0, x[f] (the same bits) elsewhere (vmc_drop_path_merge)."""
+    row, F = _check_frames("drop_path_merge: x", x), _check_index("slot", slot, x.shape[0])
+    if _check_frames("drop_path_merge: y", y) != row or y.dtype != x.dtype or y.shape[0] > F:
+        raise ValueError("drop_path_merge: y must hold at most F frames of x's row length and dtype")
+    out = torch.empty_like(x)
+    check(lib.vmc_drop_path_merge(ptr(x), ptr(y), ptr(slot), ptr(out), F, row, 1.0 - s, s, dt(x), stream()), "drop_path_merge")
+    return out
+
+
+def drop_path_merge_bwd(dout: torch.Tensor, keep: torch.Tensor, slot: torch.Tensor, s: float):
+    """(dx [F, row], dy [K, row]): dx[f] = (1 - s) dout[f] for a kept frame, dout[f] (the same bits) for a dropped one;
+    dy[j] = s dout[keep[j]] (vmc_drop_path_merge_bwd, one launch)."""
+    row, K = _check_frames("drop_path_merge_bwd: dout", dout), _check_index("keep", keep)
+    F = _check_index("slot", slot, dout.shape[0])
+    dx = torch.empty_like(dout)
+    dy = torch.empty((K, row), dtype=dout.dtype, device=dout.device)
+    check(lib.vmc_drop_path_merge_bwd(ptr(dout), ptr(keep), ptr(slot), ptr(dx), ptr(dy), F, K, row, 1.0 - s, s, dt(dout), stream()),
+          "drop_path_merge_bwd")
+    return dx, dy

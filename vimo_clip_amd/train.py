@@ -156,6 +156,29 @@ def ema_kwargs(args):
     return {"decay": float(decay), "warmup": not getattr(args, "ema_no_warmup", False)}
 
 
+def _drop_path_arg(text):
+    """``--drop_path`` values: a drop rate 0 <= p < 1."""
+    try:
+        p = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--drop_path needs a number, got {text!r}") from None
+    if not 0.0 <= p < 1.0:
+        raise argparse.ArgumentTypeError(f"--drop_path must satisfy 0 <= p < 1, got {text!r}")
+    return p
+
+
+DROP_PATH_SEED = 0x5EED0D9A      # base of the frame-draw streams of a training run; rank r draws from base + r
+
+
+def drop_path_kwargs(args, rank: int = 0) -> dict:
+    """``--drop_path P`` -> FlowStudentModel's keyword arguments; 0 (the default): none at all, the model is built exactly as before.
+    Every data-parallel rank draws from a stream of its own (the seed base is offset by the rank): ranks see different frames."""
+    p = float(getattr(args, "drop_path", 0.0) or 0.0)
+    if p == 0.0:
+        return {}
+    return {"drop_path": p, "drop_path_seed": DROP_PATH_SEED + int(rank)}
+
+
 def save_best(model, path: str) -> None:
     """The best-so-far checkpoint.  With live adapters it is written MERGED (lora.merged_state_dict: W + s B A, the reference's keys),
     so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are.  With
@@ -219,7 +242,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     model = FlowStudentModel(clip_model_name=args.clip_model_name, device=device, num_classes=args.num_classes, alpha=args.residual_alpha,
                              recompute=getattr(args, "recompute", "none"),
                              **({} if dtype_name == "bf16" else {"compute_dtype": COMPUTE_DTYPES[dtype_name]}), **lora_kwargs(args),
-                             **patch_dropout_kwargs(args, rank))
+                             **patch_dropout_kwargs(args, rank), **drop_path_kwargs(args, rank))
     arena = GradArena(model.parameters())
     parallel.broadcast_parameters(arena.flat_param)
     if world > 1:                                          # a frozen tower (LoRA) is outside the arena: it starts from rank 0's too
@@ -334,6 +357,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "on it and student_best.pth holds it; the per-epoch files keep the live weights; default off")
     p.add_argument("--ema_no_warmup", action="store_true", default=argparse.SUPPRESS,
                    help="with --ema_decay: the constant decay from the first step on, instead of min(D, (1 + t) / (10 + t))")
+    p.add_argument("--drop_path", type=_drop_path_arg, default=argparse.SUPPRESS, metavar="P",
+                   help="training only: stochastic depth per frame; residual block l of L runs on max(1, int(F (1 - P l / (L - 1)))) randomly "
+                        "drawn frames of a forward and the others skip it; evaluation runs every block on every frame; default 0 = off")
     p.add_argument("--single_label", action="store_true", help="MammalNet variant: CrossEntropy on labels.argmax(1)")
     p.add_argument("--clip_embeddings_dir", default=None, help="HDF5 file of teacher embeddings (reference layout)")
     p.add_argument("--flow_videos_dir", default=None)

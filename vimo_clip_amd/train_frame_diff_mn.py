@@ -49,6 +49,9 @@ def build_parser() -> argparse.ArgumentParser:
     arg("ema_decay", type=float, default=None, metavar="D",
         help="evaluate and write the best checkpoint with an exponential moving average of the weights (train.ema_kwargs); default off")
     arg("ema_no_warmup", action="store_true", help="with --ema_decay: the constant decay from the first step on")
+    arg("drop_path", type=float, default=0.0, metavar="P",
+        help="training only: stochastic depth per frame, block l of L runs on max(1, int(F (1 - P l / (L - 1)))) random frames "
+             "(train.drop_path_kwargs); 0 = off")
     arg("device_resize", action="store_true", help="upload decoded u8 frames and resize them on the GPU (collate_fn_device)")
     return p
 
@@ -58,6 +61,8 @@ def train(args):
     student_train.parse_loss_scale(args.loss_scale)         # a malformed value fails before any file is opened
     if not 0.0 <= args.patch_dropout < 1.0:
         raise ValueError(f"--patch_dropout must satisfy 0 <= p < 1, got {args.patch_dropout}")
+    if not 0.0 <= args.drop_path < 1.0:
+        raise ValueError(f"--drop_path must satisfy 0 <= p < 1, got {args.drop_path}")
     student_train.ema_kwargs(args)                           # --ema_decay outside (0, 1) fails here too
     size = tuple(args.spatial_size)
     sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
