@@ -227,6 +227,48 @@ def test_layernorm_bwd_error_codes():
     assert bool((z == 0).all()) and bool((v == 0).all())          # nothing ran
 
 
+def test_layernorm_fwd_error_codes():
+    """The forward LayerNorms, rejected before any launch: a D that is no multiple of 256 or above 2048 (above 4096 for the plain
+    forward), ldx < D, an unknown 16-bit type, add+LayerNorm without y16, a second dropout without the first."""
+    rows, D, W = 4, 256, 4104                                      # buffers W wide: no D below would leave them if it did launch
+    x = torch.zeros(rows, W, device=DEV)
+    v = torch.zeros(W, device=DEV)
+    h = torch.zeros(rows, W, device=DEV, dtype=BF16)
+    y16, y32, st = empty((rows, W), BF16), empty((rows, W), F32), empty((rows,), F32)
+    p, S = L.ptr, L.stream
+
+    def add(D=D, ldx=None, y=y16, dt=None):
+        return call("vmc_add_layernorm_fwd", p(x), p(h), p(v), p(v), p(y), rows, D, D if ldx is None else ldx, D, EPS, 1, L.BF16 if dt is None else dt, S())
+
+    def add2(D=D, ldx=None, y=y16, dt=None):
+        return call("vmc_add2_layernorm_fwd", p(x), p(h), p(h), p(v), p(v), p(y), rows, D, D if ldx is None else ldx, D, D, EPS, 1,
+                    L.BF16 if dt is None else dt, S())
+
+    def pn(D=D, p1=0.0, p2=0.0, dt=None):
+        return call("vmc_postnorm_dropout_fwd", p(x), p(h), p(v), p(v), None, p(y32), p(y16), p(st), p(st), rows, D, EPS, p1, 1, p2, 2,
+                    L.BF16 if dt is None else dt, S())
+
+    def pn0(D=D, dt=None):
+        return call("vmc_postnorm_fwd", p(x), p(h), p(v), p(v), None, p(y32), p(y16), p(st), p(st), rows, D, EPS, L.BF16 if dt is None else dt, S())
+
+    def ln(D=D, ldx=None, dt=None):
+        return call("vmc_layernorm_fwd", p(x), p(v), p(v), p(y16), p(y32), p(st), p(st), rows, D, D if ldx is None else ldx, EPS, L.F32,
+                    L.BF16 if dt is None else dt, S())
+
+    for bad in (260, 2304):
+        assert add(D=bad) == E_SHAPE and add2(D=bad) == E_SHAPE and pn(D=bad) == E_SHAPE and pn0(D=bad) == E_SHAPE
+    assert ln(D=4100) == E_SHAPE and ln(D=258) == E_SHAPE
+    assert add(ldx=D - 4) == E_ALIGN and add2(ldx=D - 4) == E_ALIGN and ln(ldx=D - 4) == E_ALIGN
+    assert add(dt=7) == E_DTYPE and add2(dt=7) == E_DTYPE and pn(dt=7) == E_DTYPE and pn0(dt=7) == E_DTYPE and ln(dt=7) == E_DTYPE
+    assert add(y=None) == E_ARG and add2(y=None) == E_ARG
+    assert pn(p1=0.0, p2=0.2) == E_ARG and pn(p1=1.0) == E_ARG
+    assert add(D=260, ldx=256, dt=7) == E_SHAPE and add(ldx=D - 4, dt=7) == E_ALIGN        # the order of the checks: shape, stride, type
+    sync()
+    for t in (y16, y32, st):
+        assert bool(t.isnan().all())                               # nothing ran
+    assert bool((x == 0).all())
+
+
 # ================================================================================================ LayerNorm forwards
 @pytest.mark.parametrize("case", R.LN_FWD_CASES, ids=R.ln_fwd_case_id)
 def test_layernorm_fwd(case):

@@ -239,7 +239,7 @@ def ln_fwd_inputs(c):
 
 
 # fused residual add + LayerNorm (vmc_add_layernorm_fwd / vmc_add2_layernorm_fwd)
-ADD_LN_SHAPES = [(r, D) for D in (256, 512, 768, 1024, 1280, 1536, 2048) for r in (1, 5)] + [(8195, 256)]
+ADD_LN_SHAPES = [(r, D) for D in (256, 512, 768, 1024, 1280, 1536, 1792, 2048) for r in (1, 5)] + [(8195, 256)]
 
 
 def add_ln_inputs(rows, D, dt16, two):
@@ -258,7 +258,7 @@ def add_ln_sum_f32(t):
 
 
 # post-norm tail with dropout (vmc_postnorm_dropout_fwd) and its backward (vmc_postnorm_bwd)
-POSTNORM_SHAPES = [(r, D) for D in (256, 512, 768, 1024, 1536, 2048) for r in (1, 7)] + [(8195, 256)]
+POSTNORM_SHAPES = [(r, D) for D in (256, 512, 768, 1024, 1280, 1536, 1792, 2048) for r in (1, 7)] + [(8195, 256)]
 POSTNORM_DROPS = (((0.0, 0), (0.0, 0)), ((0.3, 1234567), (0.0, 0)), ((0.1, 987654321), (0.2, 55555)))
 # (rows, D, dy in f32, dy2 present): both widths of dy, with and without the second gradient
 POSTNORM_BWD_CASES = [(7, 256, True, True), (65, 768, False, False), (2053, 512, False, True), (9, 2048, True, False)]

@@ -1,12 +1,8 @@
 // LayerNorm forward / backward, one wave per row, fp32 statistics (gfx950).  HBM-bound: 16-byte loads.
-#include <type_traits>
-
 #include "common.h"
+#include "ln_row.h"
 
 #define LN_MAX_CHUNKS 16  // D <= 16 * 256 = 4096
-// the float4 chunks per lane of a launch, as a type: the launchers pick the kernel instantiation from the run-time D with it
-template <int N>
-using chunks = std::integral_constant<int, N>;
 
 template <typename T>
 __device__ inline float4 load4(const void* base, size_t idx, bool is_f32) {
@@ -36,7 +32,6 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const void* __restrict__ x,
   const int lane = threadIdx.x & 63;
   const int wave_global = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int nwaves = gridDim.x * 4;
-  const float invD = 1.0f / (float)D;
   float4 g[NCH], b[NCH], nv[NCH];
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
@@ -53,28 +48,17 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const void* __restrict__ x,
   };
   if (wave_global < rows) fetch(wave_global);
   for (int row = wave_global; row < rows; row += nwaves) {
-    float4 v[NCH];
+    float4 v[NCH];      // chunks at col >= D stay uninitialised and are never read: ln_row_rstd applies the same guard
     float s = 0.f;
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = c * 256 + lane * 4;
-      if (col < D) {
+    for (int c = 0; c < NCH; ++c)
+      if (c * 256 + lane * 4 < D) {
         v[c] = nv[c];
-        s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+        s += ln_chunk_sum(v[c]);
       }
-    }
     if (row + nwaves < rows) fetch(row + nwaves);
-    const float mean = wave_sum(s) * invD;
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = c * 256 + lane * 4;
-      if (col < D) {
-        const float a = v[c].x - mean, bb = v[c].y - mean, cc = v[c].z - mean, d = v[c].w - mean;
-        ss += (a * a + bb * bb) + (cc * cc + d * d);
-      }
-    }
-    const float rstd = rsqrtf(wave_sum(ss) * invD + eps);
+    const float mean = ln_row_mean<false, NCH>(s, D);
+    const float rstd = ln_row_rstd<false>(v, lane, D, mean, eps);
     if (lane == 0) {
       if (mean_out) mean_out[row] = mean;
       if (rstd_out) rstd_out[row] = rstd;
@@ -83,11 +67,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const void* __restrict__ x,
     for (int c = 0; c < NCH; ++c) {
       const int col = c * 256 + lane * 4;
       if (col < D) {
-        float4 o;
-        o.x = (v[c].x - mean) * rstd * g[c].x + b[c].x;
-        o.y = (v[c].y - mean) * rstd * g[c].y + b[c].y;
-        o.z = (v[c].z - mean) * rstd * g[c].z + b[c].z;
-        o.w = (v[c].w - mean) * rstd * g[c].w + b[c].w;
+        const float4 o = ln_row_affine(v[c], mean, rstd, g[c], b[c]);
         if (y16) store4<T>(y16, (size_t)row * D + col, false, o);
         if (y32) store4<T>(y32, (size_t)row * D + col, true, o);
       }
@@ -107,11 +87,7 @@ extern "C" int vmc_layernorm_fwd(const void* x, const float* gamma, const float*
       hipLaunchKernelGGL((ln_fwd_kernel<decltype(t), decltype(nch)::value>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, gamma, beta,
                          (uint16_t*)y16, y32, mean, rstd, rows, D, (size_t)ldx, eps, x_dtype == VMC_F32);
     };
-    if (D <= 512) launch(chunks<2>{});
-    else if (D <= 768) launch(chunks<3>{});
-    else if (D <= 1024) launch(chunks<4>{});
-    else if (D <= 2048) launch(chunks<8>{});
-    else launch(chunks<LN_MAX_CHUNKS>{});
+    ln_chunks_ceil<LN_MAX_CHUNKS>(D, launch);
     return (int)hipGetLastError();
   });
 }
@@ -160,25 +136,18 @@ __global__ void __launch_bounds__(256) add_ln_kernel(float* __restrict__ x, cons
       unpack2<T>(br[c].x, a0, a1);
       unpack2<T>(br[c].y, a2, a3);
       v[c].x += a0; v[c].y += a1; v[c].z += a2; v[c].w += a3;
-      s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+      s += ln_chunk_sum(v[c]);
       if (write_x) {
         const f32x4 t = {v[c].x, v[c].y, v[c].z, v[c].w};
         __builtin_nontemporal_store(t, (f32x4*)(x + (size_t)row * ldx + c * 256 + lane * 4));
       }
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float ss = 0.f;
+    const float mean = ln_row_mean<true, CH>(s, D);
+    const float rstd = ln_row_rstd<true>(v, lane, D, mean, eps);
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      const float p = v[c].x - mean, q = v[c].y - mean, r = v[c].z - mean, t = v[c].w - mean;
-      ss += (p * p + q * q) + (r * r + t * t);
-    }
-    const float rstd = rsqrtf(wave_sum(ss) * (1.0f / D) + eps);
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const float o0 = (v[c].x - mean) * rstd * g[c].x + b[c].x, o1 = (v[c].y - mean) * rstd * g[c].y + b[c].y;
-      const float o2 = (v[c].z - mean) * rstd * g[c].z + b[c].z, o3 = (v[c].w - mean) * rstd * g[c].w + b[c].w;
-      *(uint2*)(y16 + (size_t)row * D + c * 256 + lane * 4) = make_uint2(pack2<T>(o0, o1), pack2<T>(o2, o3));
+      const float4 o = ln_row_affine(v[c], mean, rstd, g[c], b[c]);
+      *(uint2*)(y16 + (size_t)row * D + c * 256 + lane * 4) = make_uint2(pack2<T>(o.x, o.y), pack2<T>(o.z, o.w));
     }
   }
 }
@@ -191,16 +160,7 @@ static int launch_add_ln(float* x, const void* branch0, const void* branch, cons
     hipLaunchKernelGGL((add_ln_kernel<T, decltype(ch)::value>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch0, (const uint16_t*)branch,
                        gamma, beta, (uint16_t*)y16, rows, ldx, ldb0, ldb, eps, write_x);
   };
-  switch (D / 256) {
-    case 1: launch(chunks<1>{}); break;
-    case 2: launch(chunks<2>{}); break;
-    case 3: launch(chunks<3>{}); break;
-    case 4: launch(chunks<4>{}); break;
-    case 5: launch(chunks<5>{}); break;
-    case 6: launch(chunks<6>{}); break;
-    case 8: launch(chunks<8>{}); break;
-    default: return VMC_E_SHAPE;
-  }
+  if (!ln_chunks_exact(D, launch)) return VMC_E_SHAPE;
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -271,26 +231,18 @@ __global__ void __launch_bounds__(256) postnorm_kernel(const float* __restrict__
         }
       }
       v[c].x += a0; v[c].y += a1; v[c].z += a2; v[c].w += a3;
-      s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+      s += ln_chunk_sum(v[c]);
       if (sum_out) *(float4*)(sum_out + base + c * 256) = v[c];
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float ss = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const float p = v[c].x - mean, q = v[c].y - mean, r = v[c].z - mean, t = v[c].w - mean;
-      ss += (p * p + q * q) + (r * r + t * t);
-    }
-    const float rstd = rsqrtf(wave_sum(ss) * (1.0f / D) + eps);
+    const float mean = ln_row_mean<true, CH>(s, D);
+    const float rstd = ln_row_rstd<true>(v, lane, D, mean, eps);
     if (lane == 0) {
       if (mean_out) mean_out[row] = mean;
       if (rstd_out) rstd_out[row] = rstd;
     }
 #pragma unroll
     for (int c = 0; c < CH; ++c) {
-      float4 o;
-      o.x = (v[c].x - mean) * rstd * g[c].x + b[c].x; o.y = (v[c].y - mean) * rstd * g[c].y + b[c].y;
-      o.z = (v[c].z - mean) * rstd * g[c].z + b[c].z; o.w = (v[c].w - mean) * rstd * g[c].w + b[c].w;
+      const float4 o = ln_row_affine(v[c], mean, rstd, g[c], b[c]);
       if (y32) *(float4*)(y32 + base + c * 256) = o;
       if (y16) *(uint2*)(y16 + base + c * 256) = make_uint2(pack2<T>(o.x, o.y), pack2<T>(o.z, o.w));
     }
@@ -306,15 +258,7 @@ static int launch_postnorm(const float* x, const void* branch, const float* gamm
     hipLaunchKernelGGL((postnorm_kernel<T, decltype(ch)::value>), dim3(grid), dim3(256), 0, s, x, (const uint16_t*)branch, gamma, beta, sum_out,
                        y32, (uint16_t*)y16, mean, rstd, rows, eps, p1, seed1, p2, seed2);
   };
-  switch (D / 256) {
-    case 1: launch(chunks<1>{}); break;
-    case 2: launch(chunks<2>{}); break;
-    case 3: launch(chunks<3>{}); break;
-    case 4: launch(chunks<4>{}); break;
-    case 6: launch(chunks<6>{}); break;
-    case 8: launch(chunks<8>{}); break;
-    default: return VMC_E_SHAPE;
-  }
+  if (!ln_chunks_exact(D, launch)) return VMC_E_SHAPE;
   VMC_CHECK_LAUNCH();
   return 0;
 }
@@ -494,36 +438,6 @@ extern "C" size_t vmc_layernorm_bwd_workspace_bytes(int rows, int D) {
   return (size_t)ln_bwd_grid(rows) * 2 * D * sizeof(float);
 }
 
-extern "C" int vmc_layernorm_bwd2(const void* dy, const void* dy2, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                  const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
-                                  int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream);
-extern "C" int vmc_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                 const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
-                                 int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
-  return vmc_layernorm_bwd2(dy, nullptr, x, gamma, mean, rstd, add, dx, dgamma, dbeta, rows, D, ldx, dy_dtype, x_dtype, dx_dtype, dtype16,
-                            workspace, workspace_bytes, stream);
-}
-static int ln_bwd_impl(const void* dy, const void* dy2, const void* x, const float* gamma, const float* mean, const float* rstd,
-                       const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
-                       int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream,
-                       void* dx16, float p1, uint64_t seed1, float p2, uint64_t seed2);
-extern "C" int vmc_layernorm_bwd2(const void* dy, const void* dy2, const void* x, const float* gamma, const float* mean, const float* rstd,
-                                  const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
-                                  int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
-  return ln_bwd_impl(dy, dy2, x, gamma, mean, rstd, add, dx, dgamma, dbeta, rows, D, ldx, dy_dtype, x_dtype, dx_dtype, dtype16, workspace,
-                     workspace_bytes, stream, nullptr, 0.f, 0, 0.f, 0);
-}
-// Backward of vmc_postnorm_dropout_fwd in one launch (+ the partial reduce): dsum (f32) = LN'(dy32 + dy16) on the saved pre-norm sum,
-// dbranch16 = dsum through the forward's dropout masks, cast -- what vmc_layernorm_bwd2 + vmc_cast_dropout2 (or a plain cast) did in
-// two passes over the gradient.
-extern "C" int vmc_postnorm_bwd(const void* dy, const void* dy2, const float* sum, const float* gamma, const float* mean, const float* rstd,
-                                float* dsum, void* dbranch16, float* dgamma, float* dbeta, int rows, int D, int dy_dtype, float p1,
-                                uint64_t seed1, float p2, uint64_t seed2, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!dbranch16 || p1 < 0.f || p1 >= 1.f || p2 < 0.f || p2 >= 1.f || (p2 > 0.f && p1 <= 0.f)) return VMC_E_ARG;   // as the forward
-  if (((uintptr_t)dbranch16 | (uintptr_t)dsum) & 15) return VMC_E_ALIGN;
-  return ln_bwd_impl(dy, dy2, sum, gamma, mean, rstd, nullptr, dsum, dgamma, dbeta, rows, D, D, dy_dtype, VMC_F32, VMC_F32, dtype16, workspace,
-                     workspace_bytes, stream, dbranch16, p1, seed1, p2, seed2);
-}
 static int ln_bwd_impl(const void* dy, const void* dy2, const void* x, const float* gamma, const float* mean, const float* rstd,
                        const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
                        int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream,
@@ -541,14 +455,35 @@ static int ln_bwd_impl(const void* dy, const void* dy2, const void* x, const flo
                          (float*)workspace, rows, D, (size_t)ldx, dy_dtype == VMC_F32, x_dtype == VMC_F32, dx_dtype == VMC_F32,
                          (uint16_t*)dx16, p1, seed1, p2, seed2);
     };
-    if (D <= 512) launch(chunks<2>{});
-    else if (D <= 768) launch(chunks<3>{});
-    else if (D <= 1024) launch(chunks<4>{});
-    else launch(chunks<LN_BWD_MAX_CHUNKS>{});
+    ln_chunks_ceil<LN_BWD_MAX_CHUNKS>(D, launch);
     return (int)hipGetLastError();
   });
   if (rc) return rc;
   hipLaunchKernelGGL(ln_reduce_strided_kernel, dim3((D + 15) / 16, 2), dim3(256), 0, s, (const float*)workspace, dgamma, dbeta, grid, D);
   VMC_CHECK_LAUNCH();
   return 0;
+}
+
+extern "C" int vmc_layernorm_bwd2(const void* dy, const void* dy2, const void* x, const float* gamma, const float* mean, const float* rstd,
+                                  const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
+                                  int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
+  return ln_bwd_impl(dy, dy2, x, gamma, mean, rstd, add, dx, dgamma, dbeta, rows, D, ldx, dy_dtype, x_dtype, dx_dtype, dtype16, workspace,
+                     workspace_bytes, stream, nullptr, 0.f, 0, 0.f, 0);
+}
+extern "C" int vmc_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd,
+                                 const void* add, void* dx, float* dgamma, float* dbeta, int rows, int D, int ldx, int dy_dtype,
+                                 int x_dtype, int dx_dtype, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
+  return ln_bwd_impl(dy, nullptr, x, gamma, mean, rstd, add, dx, dgamma, dbeta, rows, D, ldx, dy_dtype, x_dtype, dx_dtype, dtype16, workspace,
+                     workspace_bytes, stream, nullptr, 0.f, 0, 0.f, 0);
+}
+// Backward of vmc_postnorm_dropout_fwd in one launch (+ the partial reduce): dsum (f32) = LN'(dy32 + dy16) on the saved pre-norm sum,
+// dbranch16 = dsum through the forward's dropout masks, cast -- what vmc_layernorm_bwd2 + vmc_cast_dropout2 (or a plain cast) did in
+// two passes over the gradient.
+extern "C" int vmc_postnorm_bwd(const void* dy, const void* dy2, const float* sum, const float* gamma, const float* mean, const float* rstd,
+                                float* dsum, void* dbranch16, float* dgamma, float* dbeta, int rows, int D, int dy_dtype, float p1,
+                                uint64_t seed1, float p2, uint64_t seed2, int dtype16, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!dbranch16 || p1 < 0.f || p1 >= 1.f || p2 < 0.f || p2 >= 1.f || (p2 > 0.f && p1 <= 0.f)) return VMC_E_ARG;   // as the forward
+  if (((uintptr_t)dbranch16 | (uintptr_t)dsum) & 15) return VMC_E_ALIGN;
+  return ln_bwd_impl(dy, dy2, sum, gamma, mean, rstd, nullptr, dsum, dgamma, dbeta, rows, D, D, dy_dtype, VMC_F32, VMC_F32, dtype16, workspace,
+                     workspace_bytes, stream, dbranch16, p1, seed1, p2, seed2);
 }

@@ -3,6 +3,7 @@
 // both sides share, are in tfam_route.h.
 #pragma once
 #include "common.h"
+#include "ln_row.h"
 #include "tfam_route.h"
 
 namespace {
@@ -883,21 +884,14 @@ __global__ void __launch_bounds__(256) tf_pool_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       x[i] = *(const float4*)(row + 4 * (lane + 64 * i));
-      s += (x[i].x + x[i].y) + (x[i].z + x[i].w);
+      s += ln_chunk_sum(x[i]);
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float v = 0.f;
+    const float mean = ln_row_mean<true, NI>(s, D);
+    const float rstd = ln_row_rstd<true>(x, lane, D, mean, eps);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-      x[i].x -= mean; x[i].y -= mean; x[i].z -= mean; x[i].w -= mean;
-      v += (x[i].x * x[i].x + x[i].y * x[i].y) + (x[i].z * x[i].z + x[i].w * x[i].w);
-    }
-    const float rstd = rsqrtf(wave_sum(v) * (1.0f / D) + eps);
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      const float4 g = *(const float4*)(g1 + 4 * (lane + 64 * i)), bb = *(const float4*)(b1 + 4 * (lane + 64 * i));
-      accp[i].x += x[i].x * rstd * g.x + bb.x; accp[i].y += x[i].y * rstd * g.y + bb.y;
-      accp[i].z += x[i].z * rstd * g.z + bb.z; accp[i].w += x[i].w * rstd * g.w + bb.w;
+      const float4 o = ln_row_affine(x[i], mean, rstd, *(const float4*)(g1 + 4 * (lane + 64 * i)), *(const float4*)(b1 + 4 * (lane + 64 * i)));
+      accp[i].x += o.x; accp[i].y += o.y; accp[i].z += o.z; accp[i].w += o.w;
     }
   }
 #pragma unroll
@@ -915,22 +909,15 @@ __global__ void __launch_bounds__(256) tf_pool_kernel(const float* __restrict__ 
       x[i].x = ((p0.x + p1.x) + (p2.x + p3.x)) * invT; x[i].y = ((p0.y + p1.y) + (p2.y + p3.y)) * invT;
       x[i].z = ((p0.z + p1.z) + (p2.z + p3.z)) * invT; x[i].w = ((p0.w + p1.w) + (p2.w + p3.w)) * invT;
       if (pooled32 != nullptr) *(float4*)(pooled32 + (size_t)b * D + c) = x[i];      // training: the classifier LayerNorm's input
-      s += (x[i].x + x[i].y) + (x[i].z + x[i].w);
+      s += ln_chunk_sum(x[i]);
     }
-    const float mean = wave_sum(s) * (1.0f / D);
-    float v = 0.f;
-#pragma unroll
-    for (int i = 0; i < NI; ++i) {
-      x[i].x -= mean; x[i].y -= mean; x[i].z -= mean; x[i].w -= mean;
-      v += (x[i].x * x[i].x + x[i].y * x[i].y) + (x[i].z * x[i].z + x[i].w * x[i].w);
-    }
-    const float rstd = rsqrtf(wave_sum(v) * (1.0f / D) + eps);
+    const float mean = ln_row_mean<true, NI>(s, D);
+    const float rstd = ln_row_rstd<true>(x, lane, D, mean, eps);
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int c = 4 * (lane + 64 * i);
-      const float4 g = *(const float4*)(g2 + c), bb = *(const float4*)(b2 + c);
-      *(uint2*)(out + (size_t)b * D + c) = make_uint2(pack2<T>(x[i].x * rstd * g.x + bb.x, x[i].y * rstd * g.y + bb.y),
-                                                      pack2<T>(x[i].z * rstd * g.z + bb.z, x[i].w * rstd * g.w + bb.w));
+      const float4 o = ln_row_affine(x[i], mean, rstd, *(const float4*)(g2 + c), *(const float4*)(b2 + c));
+      *(uint2*)(out + (size_t)b * D + c) = make_uint2(pack2<T>(o.x, o.y), pack2<T>(o.z, o.w));
     }
   }
 }
