@@ -434,6 +434,37 @@ int vmc_bce_loss(const float* logits, const float* targets, float* loss, float* 
 int vmc_cross_entropy_loss(const float* logits, const long long* target_index, const float* target_prob, float* loss,
                            float* dlogits, int rows, int C, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Contrastive (symmetric InfoNCE) distillation over the in-batch similarity matrix (not in the reference).
+ * M rows (frames) of E columns, clip(i) = i / rows_per_clip; pair (i, j) is valid when clip(j) != clip(i) or j == i.
+ *   u_i = s_i / max(|s_i|, 1e-5), v_j likewise, both rounded to the 16-bit type;  z = (1 / tau) u16 v16^T   (vmc_linear);
+ *   loss = 1/(2M) sum_i [ lse_{j valid} z_ij - z_ii + lse_{j valid} z_ji - z_ii ];  dz = p_row + p_col - 2 I on valid pairs;
+ *   du = dz16 v16 / (2 M tau)   (vmc_linear, A = dz16, W = v16^T);  ds through the normalisation.
+ * Mp = M rounded up to 64 is the leading dimension of v16^T and dz16 and the row count of u16 / v16: what vmc_linear's K % 64 == 0
+ * asks for.  1 <= M <= 16384 and E % 64 == 0, VMC_E_SHAPE otherwise.  Every argument is a shape constant and nothing is read
+ * back: the chain can be captured into a graph.  The same input gives the same bits (fixed-order reductions, no atomics).
+ *
+ * vmc_contrastive_workspace_layout: byte offsets (host array of 9) of u16, v16, v16^T, z [M, Mp] f32, dz16 [M, Mp], lse_row [M],
+ *   lse_col [M] and the softmax partials inside one workspace, each on a 256-byte boundary, and the total in offsets[8] (what
+ *   vmc_contrastive_workspace_bytes returns; 0 for an unsupported shape).  vmc_contrastive_partials_bytes(M): the partials alone.
+ * vmc_contrastive_prep: student f32 [M, E] dense; teacher f32 rows read through rows_per_clip (>= 1) / teacher_clip_stride exactly
+ *   as vmc_distill_loss reads them.  Writes u16, v16 [Mp, E] (pad rows zero), vt16 [E, Mp] = the bits of v16 transposed (pad columns
+ *   zero) and inv_s [M] = 1 / max(|s_i|, 1e-5).  The three 16-bit buffers are 16-byte aligned (VMC_E_ALIGN).  Two launches.
+ * vmc_contrastive_softmax: z f32 [M, ldz], ldz >= M; only the first M columns of a row are read.  rows_per_clip >= 0, 0 = no mask.
+ *   Writes lse_row, lse_col [M] (max-subtracted log-sum-exp over the valid entries of row i / column j), loss f32[1], top1 int32[1]
+ *   (rows with z_ii >= z_ij for every valid j) and, unless dz16 is NULL, dz16 [M, Mp] with the pad columns zero.  The diagonal stays
+ *   out of every running sum and is added last, so -log p_ii and dz_ii keep their relative accuracy where p_ii is near 1.
+ *   Three launches, four with dz16.
+ * vmc_contrastive_norm_bwd: du f32 [M, E], student, inv_s -> dstudent = inv_s (du - u (u . du)) where |s| > 1e-5 and du / 1e-5 where
+ *   the clamp holds the norm.  dstudent may be du itself. */
+size_t vmc_contrastive_workspace_bytes(int M, int E);
+size_t vmc_contrastive_partials_bytes(int M);
+int vmc_contrastive_workspace_layout(int M, int E, size_t* offsets);
+int vmc_contrastive_prep(const float* student, const float* teacher, void* u16, void* v16, void* vt16, float* inv_s, int M, int E,
+                         int rows_per_clip, size_t teacher_clip_stride, int dtype16, void* stream);
+int vmc_contrastive_softmax(const float* z, int M, int ldz, int rows_per_clip, float* lse_row, float* lse_col, float* loss, int* top1,
+                            void* dz16, int dtype16, void* partials, size_t partials_bytes, void* stream);
+int vmc_contrastive_norm_bwd(const float* du, const float* student, const float* inv_s, float* dstudent, int M, int E, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * K11-K14 fused — the TFAM forward as a chain of weight-streaming launches for short clips (T, Tk <= 64,
  * d_model 512 / 768, head_dim 64 / 96; vmc_tfam_supported): AttentionLayer.forward (TFAM/models/AMO_CLIP.py:37-51) in 6 launches

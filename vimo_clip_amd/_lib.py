@@ -80,6 +80,12 @@ SIGNATURES = {
     "vmc_cast_16_to_f32": (I, [P, P, Z, I, P]),
     "vmc_loss_workspace_bytes": (Z, [I]),
     "vmc_distill_loss": (I, [P, P, P, P, I, I, I, Z, I, P, Z, P]),
+    "vmc_contrastive_workspace_bytes": (Z, [I, I]),
+    "vmc_contrastive_partials_bytes": (Z, [I]),
+    "vmc_contrastive_workspace_layout": (I, [I, I, P]),
+    "vmc_contrastive_prep": (I, [P, P, P, P, P, P, I, I, I, Z, I, P]),
+    "vmc_contrastive_softmax": (I, [P, I, I, I, P, P, P, P, P, I, P, Z, P]),
+    "vmc_contrastive_norm_bwd": (I, [P, P, P, P, I, I, P]),
     "vmc_bce_loss": (I, [P, P, P, P, I, F, P, Z, P]),
     "vmc_cross_entropy_loss": (I, [P, P, P, P, P, I, I, P, Z, P]),
     "vmc_tfam_pack_offset": (ctypes.c_longlong, [I, I, I, I, I, I]),

@@ -10,6 +10,10 @@ batch as up to N micro-batches whose gradients are summed in the arena (optim.Gr
 range: the optimiser moves to device-state mode and scales, checks and skips on the device (optim.FusedAdam.enable_loss_scaling).
 ``--ema_decay D`` (not in the reference) keeps an exponential moving average of the trained weights on the device
 (optim.FusedAdam.enable_ema): validation and ``student_best.pth`` use the average, the per-epoch files the live weights.
+``--distillation_loss_mode contrastive`` (not in the reference) replaces the frame-by-frame distillation loss by the symmetric InfoNCE
+loss over all frames of the batch (losses.distillation_loss) at ``--distill_temperature``; the epoch line gains
+``val_top1``.  Its negatives are the other clips of whatever one call sees: a micro-batch under ``--accum_steps``, a rank's shard
+under torchrun.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ import argparse
 import contextlib
 import json
 import time
+import warnings
 
 import torch
 
@@ -47,8 +52,10 @@ def split_micro_batches(batch, n):
     """Split a collated batch along its clips into at most ``n`` micro-batches for gradient accumulation: [(sub_batch, weight)].
     Chunk sizes are ``torch.chunk``'s (ceil(B / n) clips each, the last one smaller, fewer than n chunks when B does not stretch);
     tensors are split as views, per-clip lists (``video_id``) are sliced alike, anything else is passed to every chunk.  weight =
-    chunk clips / batch clips: the student's losses are means over rows and no operator couples the clips of a batch, so the
-    weighted sum of the micro-batch gradients is the batch's gradient.  n = 1 returns the batch itself with weight 1."""
+    chunk clips / batch clips: the student's losses are means over rows and, the contrastive distillation mode apart, no operator
+    couples the clips of a batch, so the weighted sum of the micro-batch gradients is the batch's gradient.  (In the contrastive mode
+    every micro-batch draws its negatives from its own clips: the sum is a gradient, but not the batch's; `train` warns.)  n = 1
+    returns the batch itself with weight 1."""
     n = int(n)
     if n < 1:
         raise ValueError(f"split_micro_batches: n must be at least 1, got {n}")
@@ -179,6 +186,17 @@ def drop_path_kwargs(args, rank: int = 0) -> dict:
     return {"drop_path": p, "drop_path_seed": DROP_PATH_SEED + int(rank)}
 
 
+def distill_kwargs(args) -> dict:
+    """``--distillation_loss_mode contrastive [--distill_temperature T]`` -> the keyword arguments of ``distillation_loss`` beside the
+    mode: the temperature, and ``--compute_dtype`` for the logits' operands.  Any other mode: none at all, the call is the one it was."""
+    if getattr(args, "distillation_loss_mode", "cosine") != "contrastive":
+        return {}
+    tau = float(getattr(args, "distill_temperature", 0.07))
+    if not tau > 0.0:
+        raise ValueError(f"--distill_temperature must be positive, got {tau}")
+    return {"temperature": tau, "compute_dtype": COMPUTE_DTYPES[getattr(args, "compute_dtype", "bf16")]}
+
+
 def save_best(model, path: str) -> None:
     """The best-so-far checkpoint.  With live adapters it is written MERGED (lora.merged_state_dict: W + s B A, the reference's keys),
     so that it loads into the reference and runs the inference path; the per-epoch files keep the adapters as they are.  With
@@ -201,17 +219,28 @@ def _class_loss(logits, labels, class_positive_weight, single_label):
 
 
 def evaluate(model, val_set, device, distillation_loss_mode, class_positive_weight, batch_size, rank=0, world=1, single_label=False,
-             collate=collate_fn, forward_kwargs=None):
+             collate=collate_fn, forward_kwargs=None, distill_kwargs=None, metrics=None):
+    """(distillation, classification, total) validation loss, means over the batches.  distill_kwargs: `distill_kwargs(args)`;
+    metrics: a dict that receives ``val_top1`` -- the mean over the batches of the share of frames whose own teacher frame has the
+    largest logit in the batch -- in the contrastive mode, and nothing in any other."""
     model.eval()
+    contrastive = distillation_loss_mode == "contrastive"
     tot = torch.zeros(4, device=device)
+    top1 = torch.zeros(1, device=device)
     with torch.no_grad():
         for batch in _batches(val_set, batch_size, rank, world, collate):
             _, emb_d, logits = model(_frames(batch).to(device), **(forward_kwargs or {}))
-            dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=distillation_loss_mode)
+            dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=distillation_loss_mode, **(distill_kwargs or {}),
+                                   **({"return_top1": True} if contrastive else {}))
+            if contrastive:
+                dl, frac = dl
+                top1 += frac
             cl = _class_loss(logits, batch["labels"].to(device), class_positive_weight, single_label)
             tot += torch.stack([dl, cl, dl + cl, torch.ones((), device=device)])
     tot = parallel.all_reduce_scalars(tot)
     n = max(1.0, float(tot[3]))
+    if contrastive and metrics is not None:
+        metrics["val_top1"] = float(parallel.all_reduce_scalars(top1)[0]) / n
     return float(tot[0]) / n, float(tot[1]) / n, float(tot[2]) / n
 
 
@@ -223,7 +252,12 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
     if accum < 1:                                           # before anything touches the device
         raise ValueError(f"--accum_steps must be at least 1, got {accum}")
     ema = ema_kwargs(args)
+    dkw = distill_kwargs(args)                               # a temperature that is not positive fails here
     rank, world, local = parallel.init_from_env()
+    if dkw and (accum > 1 or world > 1):
+        warnings.warn("contrastive distillation draws its negatives from the clips of one call: with --accum_steps > 1 or more than one "
+                      "rank they come from the micro-batch or the rank's shard alone, and the summed gradient is not the gradient of "
+                      "the whole batch's contrastive loss", stacklevel=2)
     device = f"cuda:{local}"
     E = embed_dim(args.clip_model_name)
     single = bool(getattr(args, "single_label", False))
@@ -261,7 +295,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
 
     def micro_loss(batch):
         emb, emb_d, logits = model(_frames(batch).to(device), **forward_kwargs)
-        dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
+        dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode, **dkw)
         return dl + _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
     best = float("inf")
     ckpt_dir = getattr(args, "checkpoint_dir", None)       # reference: checkpoints/<run timestamp> (train.py:69-74)
@@ -290,7 +324,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
                 nframes += frames.shape[0] * frames.shape[1]
                 continue
             emb, emb_d, logits = model(frames.to(device), **forward_kwargs)
-            dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode)
+            dl = distillation_loss(emb_d, batch["rgb_emb"].to(device)[:, :-1, :], mode=args.distillation_loss_mode, **dkw)
             cl = _class_loss(logits, batch["labels"].to(device), args.class_positive_weight, single)
             optimizer.scale_loss(dl + cl).backward()
             optimizer.step(grad_scale=reducer.all_reduce(), max_grad_norm=None if single else args.grad_clip_norm)
@@ -299,9 +333,10 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
         if rank == 0 and ckpt_dir:                          # train.py:164-172: every epoch (the live weights) + the best-so-far copy
             from .checkpoint import save_state_dict
             save_state_dict(model, f"{ckpt_dir}/student_epoch_{epoch + 1}.pth")
+        extra = {}
         with averaged():
             vd, vc, vt = evaluate(model, val_set, device, args.distillation_loss_mode, args.class_positive_weight, args.batch_size, rank, world,
-                                  single, collate, forward_kwargs)
+                                  single, collate, forward_kwargs, **({"distill_kwargs": dkw, "metrics": extra} if dkw else {}))
             if rank == 0 and ckpt_dir and vt < best:
                 save_best(model, f"{ckpt_dir} - best/student_best.pth")
         best = min(best, vt)
@@ -315,6 +350,7 @@ def train(args, datasets=None, collate=collate_fn, forward_kwargs=None):
                 line["loss_scale"], line["skipped_steps"] = float(rec.view(torch.float32)[0]), int(rec[7])
             if ema is not None:                             # the validation figures are those of the averaged weights
                 line["ema"] = True
+            line.update(extra)                              # val_top1, in the contrastive mode only
             print(json.dumps(line), flush=True)
     return best
 
@@ -328,7 +364,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sequence_length", type=int, default=17)
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--learning_rate", type=float, default=1e-3)
-    p.add_argument("--distillation_loss_mode", default="cosine")
+    p.add_argument("--distillation_loss_mode", default="cosine", help="cosine or mse as in the reference; contrastive: symmetric InfoNCE over "
+                   "all frames of the batch, the other frames of a frame's own clip masked out as negatives")
+    # absent unless given (distill_kwargs reads it with its default), like the other options the reference does not have
+    p.add_argument("--distill_temperature", type=float, default=argparse.SUPPRESS, metavar="T",
+                   help="temperature of the contrastive mode's logits cos(student_i, teacher_j) / T; default 0.07")
     p.add_argument("--class_positive_weight", type=int, default=9)
     p.add_argument("--residual_alpha", type=float, default=0.1)
     p.add_argument("--grad_clip_norm", type=float, default=None)

@@ -23,7 +23,9 @@ def build_parser() -> argparse.ArgumentParser:
     arg("batch_size", type=int, default=32)
     arg("num_workers", type=int, default=4, help="accepted for the reference's command lines; batches are assembled in-process")
     arg("learning_rate", type=float, default=1e-3)
-    arg("distillation_loss_mode", default="cosine", choices=["cosine", "mse"])
+    arg("distillation_loss_mode", default="cosine", choices=["cosine", "mse", "contrastive"],
+        help="contrastive: symmetric InfoNCE over all frames of the batch (train.distill_kwargs)")
+    arg("distill_temperature", type=float, default=0.07, metavar="T", help="temperature of the contrastive mode's logits")
     arg("num_classes", type=int, default=12)
     arg("sequence_length", type=int, default=30)
     arg("residual_alpha", type=float, default=0.1)
@@ -64,6 +66,7 @@ def train(args):
     if not 0.0 <= args.drop_path < 1.0:
         raise ValueError(f"--drop_path must satisfy 0 <= p < 1, got {args.drop_path}")
     student_train.ema_kwargs(args)                           # --ema_decay outside (0, 1) fails here too
+    student_train.distill_kwargs(args)                       # and so does a temperature that is not positive
     size = tuple(args.spatial_size)
     sets = tuple(HDF5VideoDataset(path, args.frame_diff_videos_dir, sequence_length=args.sequence_length, spatial_size=size,
                                   raw_u8=args.device_resize) for path in (args.train_hdf5_path, args.val_hdf5_path))
